@@ -24,6 +24,19 @@ Extra workloads (same JSON contract, run explicitly):
                              5-model ensemble predict -> D2H labels
     --workload rf-fit        level-synchronous histogram forest build
 
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, print the result line.  Two options add to that:
+    --full               also run the untimed extras of the workload (the RF
+                         flagship's 5-class accuracy on the shipped rows and
+                         the 6-class refit + accuracy) and report them in
+                         the result line's "config"
+    --dump-outputs DIR   after the timed steps, write what the last timed
+                         step returned as DIR/<name>.npy (float32/float64,
+                         <= 64 MB in all; larger outputs are written as a
+                         fixed seeded sample).  Inputs depend only on the
+                         arguments, so two builds can be compared output
+                         for output.
+
 The forest/model shapes are the reference's own checkpoints (converted to
 data/ref_models/*.npz), so model config matches the named baseline; data is
 synthetic (no network for datasets) with the real rows' scale/jitter.
@@ -62,6 +75,13 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 RF_CKPT = os.path.join(REPO, "data", "ref_models", "RandomForestClassifier.npz")
 
 
+# what the last timed step returned (kept for --dump-outputs)
+_LAST_OUTPUT = [None]
+
+# --dump-outputs budget for all arrays of one run together
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
 def _timed(step, steps: int, warmup: int, use_gpu: bool) -> float:
     """Warmup, barrier+sync, time K steps, barrier+sync; MAX over ranks."""
     for _ in range(warmup):
@@ -69,9 +89,10 @@ def _timed(step, steps: int, warmup: int, use_gpu: bool) -> float:
     if use_gpu:
         torch.cuda.synchronize()
     dist.barrier()
+    out = None
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        out = step()
     if use_gpu:
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
@@ -81,7 +102,42 @@ def _timed(step, steps: int, warmup: int, use_gpu: bool) -> float:
     if dist.is_initialized():
         torch.distributed.all_reduce(e, op=torch.distributed.ReduceOp.MAX)
     dist.barrier()
+    _LAST_OUTPUT[0] = out
     return float(e[0])
+
+
+def _dump_outputs(args, rank: int, arrays: dict) -> None:
+    """Write the last timed step's outputs as <--dump-outputs>/<name>.npy
+    (rank 0's shard on a multi-rank run; no-op without the option).
+
+    Floating arrays keep float32/float64; everything else (label indices,
+    counts) is written as float32 when every value is exactly representable
+    there, else float64.  When the arrays together exceed DUMP_MAX_BYTES each
+    is cut to its share of the budget by a seeded, sorted row sample, so the
+    same arguments always pick the same rows.
+    """
+    out_dir, seed = args.dump_outputs, args.seed
+    if not out_dir or rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            exact32 = a.size == 0 or float(np.abs(a).max()) <= 2.0 ** 24
+            a = a.astype(np.float32 if exact32 else np.float64)
+        conv[name] = a.reshape(-1) if a.ndim == 0 else a
+    share = DUMP_MAX_BYTES // max(1, len(conv))
+    over = sum(v.nbytes for v in conv.values()) > DUMP_MAX_BYTES
+    for name, a in conv.items():
+        if over and a.nbytes > share:
+            row_bytes = max(1, a.nbytes // a.shape[0])
+            keep = max(1, share // row_bytes)
+            idx = np.sort(np.random.default_rng(seed).choice(a.shape[0], size=keep, replace=False))
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def _emit(rank, metric, value, unit, world, args, ms_per_step, scaling, config):
@@ -110,24 +166,38 @@ def _emit(rank, metric, value, unit, world, args, ms_per_step, scaling, config):
 
 def bench_rf(args, rank, world, device, use_gpu):
     model = load_model(RF_CKPT, device=device)
-    # measured (non-timed) accuracies, reference split protocol.  The
-    # reference's 6_quake_training_data.csv is NOT shipped (SURVEY §2.1
-    # C11), so the shipped rows cover 5 classes; the 6-class number refits
-    # on shipped rows + synthetic quake (D-ITG Quake3 replay through the
-    # real collection path) and is labelled _quake_synth accordingly.
     X_real, y_real = load_reference_dataset()
-    _, Xte, _, yte = train_test_split_ref(X_real, y_real)
-    acc5 = accuracy(yte, model.predict(Xte))
-    from traffic_classifier_sdn_amd.models import RandomForestClassifier
-    from traffic_classifier_sdn_amd.utils.datasets import load_six_class_dataset
+    config = {
+        "model": "RandomForestClassifier-100trees-6class",
+        "global_batch": args.rows_per_gpu * world,
+        "seq_len": 12,
+        "parallelism": f"dp{world}",
+        "dtype_note": "f32 features/thresholds, prediction-parity-tested vs f64 sklearn oracles; fit paths accumulate f64",
+    }
+    if args.full:
+        # measured (non-timed) accuracies, reference split protocol.  The
+        # reference's 6_quake_training_data.csv is NOT shipped (SURVEY §2.1
+        # C11), so the shipped rows cover 5 classes; the 6-class number refits
+        # on shipped rows + synthetic quake (D-ITG Quake3 replay through the
+        # real collection path) and is labelled _quake_synth accordingly.
+        _, Xte, _, yte = train_test_split_ref(X_real, y_real)
+        acc5 = accuracy(yte, model.predict(Xte))
+        from traffic_classifier_sdn_amd.models import RandomForestClassifier
+        from traffic_classifier_sdn_amd.utils.datasets import load_six_class_dataset
 
-    X6, y6 = load_six_class_dataset(seed=args.seed)
-    Xtr6, Xte6, ytr6, yte6 = train_test_split_ref(X6, y6)
-    m6 = RandomForestClassifier(
-        n_estimators=100, seed=args.seed,
-        builder="hist" if use_gpu else "exact", device=device,
-    ).fit(Xtr6, ytr6)
-    acc6 = accuracy(yte6, m6.predict(Xte6))
+        X6, y6 = load_six_class_dataset(seed=args.seed)
+        Xtr6, Xte6, ytr6, yte6 = train_test_split_ref(X6, y6)
+        m6 = RandomForestClassifier(
+            n_estimators=100, seed=args.seed,
+            builder="hist" if use_gpu else "exact", device=device,
+        ).fit(Xtr6, ytr6)
+        acc6 = accuracy(yte6, m6.predict(Xte6))
+        config.update({
+            "accuracy_6class_quake_synth": acc6,
+            "accuracy_5class_shipped": acc5,
+            "accuracy_published_ref_6class": 0.9987,
+            "quake_note": "reference's 6_quake_training_data.csv (1244 rows) is not shipped; 6th class synthesized via D-ITG Quake3 replay (utils.datasets.synthesize_quake_rows)",
+        })
 
     Xn = synthetic_flow_rows(args.rows_per_gpu, seed=args.seed + 1000 * rank, reference_X=X_real)
     X = torch.from_numpy(Xn).to(device)
@@ -136,6 +206,8 @@ def bench_rf(args, rank, world, device, use_gpu):
 
     elapsed = _timed(lambda: model.predict_index(X), args.steps, args.warmup, use_gpu)
     total_rows = args.rows_per_gpu * world * args.steps
+    # what a caller of predict_index receives: one class index per row
+    _dump_outputs(args, rank, {"rf_predict_index": _LAST_OUTPUT[0]})
     _emit(
         rank,
         "flows/sec, RandomForest 100-tree 6-class predict on synthetic flow-stat rows",
@@ -145,17 +217,7 @@ def bench_rf(args, rank, world, device, use_gpu):
         args,
         elapsed / args.steps * 1000.0,
         "weak",
-        {
-            "model": "RandomForestClassifier-100trees-6class",
-            "global_batch": args.rows_per_gpu * world,
-            "seq_len": 12,
-            "parallelism": f"dp{world}",
-            "accuracy_6class_quake_synth": acc6,
-            "accuracy_5class_shipped": acc5,
-            "accuracy_published_ref_6class": 0.9987,
-            "quake_note": "reference's 6_quake_training_data.csv (1244 rows) is not shipped; 6th class synthesized via D-ITG Quake3 replay (utils.datasets.synthesize_quake_rows)",
-            "dtype_note": "f32 features/thresholds, prediction-parity-tested vs f64 sklearn oracles; fit paths accumulate f64",
-        },
+        config,
     )
 
 
@@ -178,6 +240,7 @@ def bench_knn(args, rank, world, device, use_gpu):
 
     elapsed = _timed(lambda: m.predict_index(Q), args.steps, args.warmup, use_gpu)
     total_q = args.knn_queries * world * args.steps
+    _dump_outputs(args, rank, {"knn_predict_index": _LAST_OUTPUT[0]})
     _emit(
         rank,
         "queries/sec, KNeighbors k=5 brute-force over sharded reference set (RCCL all-gather top-k)",
@@ -220,11 +283,14 @@ def bench_svc_fit(args, rank, world, device, use_gpu):
     done = []
 
     def step():
-        _, _, it = smo_fit_pair(X, yt, C=1.0, gamma=gamma, tol=0.0, max_iter=iters)
+        alpha, b, it = smo_fit_pair(X, yt, C=1.0, gamma=gamma, tol=0.0, max_iter=iters)
         done.append(it)
+        return alpha, b
 
     elapsed = _timed(step, args.steps, args.warmup, use_gpu)
     timed_iters = sum(done[args.warmup :])
+    alpha, b = _LAST_OUTPUT[0]
+    _dump_outputs(args, rank, {"svc_fit_alpha": alpha, "svc_fit_intercept": np.float64(b)})
     # each SMO iteration updates the full gradient: n_total fused kernel-row
     # evaluations -> row-updates/s is the scale-invariant rate
     row_updates = float(timed_iters) * n_total / max(1, world) * world
@@ -288,6 +354,10 @@ def bench_svc_fit_full(args, rank, world, device, use_gpu):
 
     elapsed = _timed(step, args.steps, args.warmup, use_gpu)
     m = fitted[-1]
+    _dump_outputs(args, rank, {
+        "svc_full_n_iter": np.asarray(m.n_iter_),
+        "svc_full_n_support": m.n_support_,
+    })
     # held-out evaluation (untimed), fresh class-conditional rows
     Xe, lab_e, _ = _stratified_synth_rows(50_000 if use_gpu else 2_000, args.seed + 31337)
     pred = m.predict(Xe)
@@ -333,12 +403,15 @@ def bench_rf_fit(args, rank, world, device, use_gpu):
     trees = args.rf_fit_trees
 
     def step():
-        RandomForestClassifier(
+        return RandomForestClassifier(
             n_estimators=trees, seed=args.seed,
             builder="hist" if use_gpu else "exact", device=device,
         ).fit(Xn, y)
 
     elapsed = _timed(step, args.steps, args.warmup, use_gpu)
+    if args.dump_outputs:
+        # the fitted forest, seen through its votes on the training rows
+        _dump_outputs(args, rank, {"rf_fit_predict_index": _LAST_OUTPUT[0].predict_index(Xn)})
     total = float(n) * trees * args.steps  # trees are split across ranks
     _emit(
         rank,
@@ -399,11 +472,13 @@ def bench_serve(args, rank, world, device, use_gpu):
     lat = []
 
     def step():
-        eng.classify(table)
+        out = eng.classify(table)
         lat.append(eng.last_latency_s)
+        return out
 
     elapsed = _timed(step, args.steps, args.warmup, use_gpu)
     lat_t = np.asarray(lat[args.warmup :])
+    _dump_outputs(args, rank, {"serve_" + k: v for k, v in _LAST_OUTPUT[0].items()})
     _emit(
         rank,
         "flows/sec through full poll cycle (snapshot->hipGraph ensemble predict->labels), 5-model ensemble",
@@ -483,6 +558,13 @@ def main() -> int:
     ap.add_argument("--rf-fit-rows", type=int, default=1_000_000)
     ap.add_argument("--rf-fit-trees", type=int, default=25)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the workload's untimed extras (RF flagship: "
+                         "5-class accuracy + 6-class refit accuracy) and report "
+                         "them in the result line; a plain run skips them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy "
+                         "(float32/float64, at most 64 MB in all)")
     args = ap.parse_args()
 
     spawned = _maybe_self_spawn(args)

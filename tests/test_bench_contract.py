@@ -17,6 +17,7 @@ REQUIRED = [
 
 CASES = {
     "rf": ["--steps", "2", "--warmup", "1"],
+    "rf-full": ["--full", "--steps", "2", "--warmup", "1"],
     "knn": ["--workload", "knn", "--steps", "2", "--warmup", "1", "--knn-queries", "2048"],
     "knn-approx": ["--workload", "knn", "--knn-approx", "--steps", "2", "--warmup", "1",
                    "--knn-queries", "2048"],
@@ -44,6 +45,50 @@ def test_bench_emits_driver_contract(name):
     assert isinstance(d["config"], dict) and d["config"]
     assert d["scaling"] in ("weak", "strong")
     assert d["data"] == "synthetic"
+    assert d["steps"] == int(CASES[name][CASES[name].index("--steps") + 1])
+    assert d["ms_per_step"] > 0
+    # the untimed accuracy extras of the flagship live behind --full only
+    extras = {"accuracy_5class_shipped", "accuracy_6class_quake_synth"}
+    if name == "rf-full":
+        assert extras <= set(d["config"])
+        assert d["config"]["accuracy_5class_shipped"] > 0.99
+    elif name == "rf":
+        assert not extras & set(d["config"])
+
+
+def test_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's outputs as float .npy
+    files, identical from run to run for identical arguments, and equal to
+    what the model predicts on the same seeded rows."""
+    import numpy as np
+
+    dumps = []
+    for tag in ("a", "b"):
+        out = tmp_path / tag
+        r = subprocess.run(
+            [sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1",
+             "--rows-per-gpu", "5000", "--dump-outputs", str(out)],
+            cwd=REPO, capture_output=True, text=True, timeout=300,
+        )
+        assert r.returncode == 0, r.stderr[-1500:]
+        d = json.loads(r.stdout.strip().splitlines()[-1])
+        assert d["steps"] == 2 and d["ms_per_step"] > 0
+        files = sorted(os.listdir(out))
+        assert files == ["rf_predict_index.npy"]
+        dumps.append(np.load(out / files[0]))
+    a, b = dumps
+    assert a.dtype in (np.float32, np.float64)
+    assert a.shape == (5000,) and a.nbytes <= 64_000_000
+    np.testing.assert_array_equal(a, b)
+
+    from traffic_classifier_sdn_amd.models import load_model
+    from traffic_classifier_sdn_amd.utils.datasets import load_reference_dataset, synthetic_flow_rows
+
+    X_real, _ = load_reference_dataset()
+    X = synthetic_flow_rows(5000, seed=0, reference_X=X_real)
+    m = load_model(os.path.join(REPO, "data", "ref_models", "RandomForestClassifier.npz"), device="cpu")
+    np.testing.assert_array_equal(a, m.predict_index(X).cpu().numpy())
+    assert len(np.unique(a)) > 1
 
 
 def _run_multirank(extra, n, timeout=420):

@@ -21,8 +21,8 @@ from traffic_classifier_sdn_amd.models import (
 from traffic_classifier_sdn_amd.utils import checkpoint as ckpt
 from traffic_classifier_sdn_amd.utils.metrics import accuracy
 
-REF_MODELS = "/root/reference/models"
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="reference mount absent")
+# the six shipped sklearn-1.0.1 checkpoints, stored as test fixtures
+REF_MODELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_models")
 
 
 def _sklearn_load(name):
@@ -36,7 +36,6 @@ def _sklearn_load(name):
 # ----------------------------------------------------------------------
 
 
-@needs_ref
 def test_logistic_predict_parity(dataset):
     X, _ = dataset
     ours = load_model(os.path.join(REF_MODELS, "LogisticRegression"), device="cpu")
@@ -44,7 +43,6 @@ def test_logistic_predict_parity(dataset):
     np.testing.assert_array_equal(ours.predict(X), sk.predict(X))
 
 
-@needs_ref
 def test_gnb_predict_parity(dataset):
     X, _ = dataset
     ours = load_model(os.path.join(REF_MODELS, "GaussianNB"), device="cpu")
@@ -54,7 +52,6 @@ def test_gnb_predict_parity(dataset):
     assert (a == b).mean() > 0.999
 
 
-@needs_ref
 def test_kmeans_predict_parity(dataset):
     X, _ = dataset
     ours = load_model(os.path.join(REF_MODELS, "KMeans_Clustering"), device="cpu")
@@ -65,7 +62,6 @@ def test_kmeans_predict_parity(dataset):
     assert (a == b).mean() > 0.999
 
 
-@needs_ref
 def test_svc_predict_parity(dataset):
     X, _ = dataset
     ours = load_model(os.path.join(REF_MODELS, "SVC"), device="cpu")
@@ -75,7 +71,6 @@ def test_svc_predict_parity(dataset):
     assert (a == b).mean() > 0.999
 
 
-@needs_ref
 def test_kneighbors_predict_parity_fresh_fit(split):
     # the shipped KNeighbors pickle is unloadable by modern sklearn; oracle
     # is a fresh sklearn brute-force fit round-tripped through our shadow
@@ -91,7 +86,6 @@ def test_kneighbors_predict_parity_fresh_fit(split):
     assert (a == b).mean() > 0.999
 
 
-@needs_ref
 def test_kneighbors_shipped_checkpoint_accuracy(split):
     # shipped checkpoint loads through the shadow reader and reproduces the
     # published 99.30% held-out accuracy on the fit data
@@ -103,7 +97,6 @@ def test_kneighbors_shipped_checkpoint_accuracy(split):
     assert acc > 0.97
 
 
-@needs_ref
 def test_rf_predict_parity_fresh_fit(split):
     from sklearn.ensemble import RandomForestClassifier as SK
 
@@ -118,7 +111,6 @@ def test_rf_predict_parity_fresh_fit(split):
     assert (a == b).mean() > 0.999
 
 
-@needs_ref
 def test_rf_shipped_checkpoint_accuracy(split):
     ours = load_model(os.path.join(REF_MODELS, "RandomForestClassifier"), device="cpu")
     Xtr, Xte, ytr, yte = split

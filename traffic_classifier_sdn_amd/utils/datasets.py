@@ -66,10 +66,12 @@ def load_reference_dataset(
     notebooks).  Returns (X, y); X has the 12 model features when
     ``features_only`` (cumulative columns dropped), else all 16.
 
-    Falls back to the packed in-repo copy when the reference mount is absent
-    (e.g. on a GPU box).
+    Without ``data_dir`` the packed in-repo copy (the same rows, bit for bit)
+    is used when present, so results never depend on files outside the
+    repository; the CSV directory is only read when asked for explicitly or
+    when the packed copy is missing.
     """
-    if data_dir is None and not os.path.isdir(REFERENCE_DATASET_DIR) and os.path.exists(PACKED_DATASET):
+    if data_dir is None and os.path.exists(PACKED_DATASET):
         return load_packed_dataset(features_only=features_only)
     data_dir = data_dir or REFERENCE_DATASET_DIR
     Xs, ys = [], []
@@ -91,7 +93,7 @@ def load_reference_dataset(
 
 
 def save_packed_dataset(path: str = PACKED_DATASET) -> None:
-    X, y = load_reference_dataset(features_only=False)
+    X, y = load_reference_dataset(data_dir=REFERENCE_DATASET_DIR, features_only=False)
     np.savez_compressed(path, X=X, y=y.astype(str))
 
 
