@@ -27,8 +27,9 @@ void launch_linear_argmax(const float*, const float*, const float*, int*,
                           long long, int, hipStream_t);
 void launch_kmeans_assign(const float*, const float*, int*, double*, double*,
                           double*, long long, int, int, hipStream_t);
-void launch_rf_predict(const float*, const unsigned*, const int*, const float*,
-                       int*, long long, int, int, int, int, hipStream_t);
+void launch_rf_predict(const float*, const unsigned*, const unsigned*,
+                       const int*, const float*, int*, long long, int, int,
+                       int, int, hipStream_t);
 void launch_svc_predict(const float*, const float*, const float*,
                         const unsigned char*, const float*, int*, long long,
                         int, int, float, hipStream_t);
@@ -132,20 +133,28 @@ static std::vector<torch::Tensor> kmeans_assign(torch::Tensor X,
 }
 
 static torch::Tensor rf_predict(torch::Tensor X, torch::Tensor nodes,
-                                torch::Tensor roots, torch::Tensor leaf_proba,
-                                int64_t n_leaves, int64_t C) {
+                                torch::Tensor snodes, torch::Tensor roots,
+                                torch::Tensor leaf_proba, int64_t n_leaves,
+                                int64_t C) {
   CHECK_IN(X, torch::kFloat32);
-  CHECK_IN(nodes, torch::kInt32);  // packed uint2 as 2x int32
+  CHECK_IN(nodes, torch::kInt32);   // packed uint2 as 2x int32
+  CHECK_IN(snodes, torch::kInt32);  // streaming kernel's table (ops/gpu.py)
   CHECK_IN(roots, torch::kInt32);
   CHECK_IN(leaf_proba, torch::kFloat32);
   TORCH_CHECK(X.size(1) == 12, "X must be (n,12)");
   TORCH_CHECK(nodes.size(1) == 2, "nodes must be (n_nodes,2) int32");
+  TORCH_CHECK(snodes.dim() == 2 && snodes.size(1) == 2 &&
+                  snodes.size(0) == nodes.size(0) + 2,
+              "snodes must be (n_nodes+2,2) int32");
+  TORCH_CHECK(leaf_proba.numel() >= n_leaves * C,
+              "leaf_proba must hold n_leaves rows of C");
   const long long n = X.size(0);
   const int n_nodes = nodes.size(0);
   const int T = roots.size(0);
   auto out = torch::empty({n}, X.options().dtype(torch::kInt32));
   launch_rf_predict(X.data_ptr<float>(),
                     reinterpret_cast<const unsigned*>(nodes.data_ptr<int>()),
+                    reinterpret_cast<const unsigned*>(snodes.data_ptr<int>()),
                     roots.data_ptr<int>(), leaf_proba.data_ptr<float>(),
                     out.data_ptr<int>(), n, n_nodes, (int)n_leaves, T, (int)C,
                     cur_stream());

@@ -213,6 +213,16 @@ DEV float sel12(const Row12& x, unsigned f) {
   return (q & 2u) ? q2 : lo;
 }
 
+// Pure-leaf votes of class c out of the packed register (10 bits per class).
+// Only classes 0..5 have a field: rf_pack gives a forest with more classes
+// no pure leaves, and a shift past bit 63 must not even be formed (c is a
+// compile-time constant in every caller's unrolled loop).  The u32 cast
+// keeps the convert a single instruction.
+DEV float vote_count(unsigned long long votes, int c) {
+  return c * 10 + 10 <= 64 ? (float)(unsigned)((votes >> (c * 10)) & 1023ull)
+                           : 0.f;
+}
+
 // Traversal body shared by the four table-placement variants.  LDS_NODES /
 // LDS_PROBS are compile-time so the node fetch lowers to ds_read_b64 (LDS)
 // or global_load_dwordx2 — a runtime ternary over the two pointers would
@@ -296,7 +306,7 @@ __global__ void rf_predict_kernel(const float* __restrict__ X,
           float m1 = -INFINITY, m2 = -INFINITY;
 #pragma unroll
           for (int c = 0; c < C; ++c) {
-            float sc = acc[c] + (float)((votes >> (c * 10)) & 1023ull);
+            float sc = acc[c] + vote_count(votes, c);
             if (sc > m1) { m2 = m1; m1 = sc; }
             else if (sc > m2) m2 = sc;
           }
@@ -309,137 +319,160 @@ __global__ void rf_predict_kernel(const float* __restrict__ X,
     int bi = 0;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-      float sc = acc[c] + (float)((votes >> (c * 10)) & 1023ull);
+      float sc = acc[c] + vote_count(votes, c);
       if (sc > best) { best = sc; bi = c; }
     }
     out[row] = bi;
   }
 }
 
-// ILP-2 variant (mode 3): two independent traversal chains per lane.  At
-// mode 2 the kernel is latency-bound (VALUBusy 57.5%, SQ_WAIT_ANY 68% of
-// wave cycles parked on the L2 node fetch + LDS feature read chains) and
-// the 32-waves/CU cap is already reached — more memory-level parallelism
-// has to come from within the wave.  256-thread blocks keep the two
-// pitch-13 feature slabs at the same 26.6 KB the 512-thread single-row
-// variant used, so occupancy is unchanged and each CU runs 2x the chains.
-template <int C>
-__launch_bounds__(256, 1)
-__global__ void rf_predict_ilp2_kernel(const float* __restrict__ X,
-                                       const uint2* __restrict__ nodes,
-                                       const int* __restrict__ roots,
-                                       const float* __restrict__ leaf_proba,
-                                       int* __restrict__ out, long long n,
-                                       int T) {
+// Streaming variant (mode 4, the large-batch default): a LANE, not a wave,
+// is the unit that advances through trees and rows.  The row-per-lane
+// kernel above reconverges after every tree and leaves together, so a wave
+// pays the deepest path of its 64 lanes in every tree and the slowest row's
+// exit: 765 node visits per row where the row itself needs 322
+// (profiles/rf_predict_stream.md).  Here each lane carries
+// (row, t, idx, acc, votes) and one loop iteration is one node visit for
+// every lane, with no exec masking and no per-lane bookkeeping in it:
+//
+//  * It walks rf_pack's STREAM table (layout there).  A leaf's link is the
+//    next tree's root, so a lane steps from leaf to root with no roots[]
+//    load; a leaf "goes right" because its byte is clamped to slot 12 of the
+//    lane's pitch-13 LDS row, which holds NaN.
+//  * The leaf byte carries the vote shift, so the pure-leaf count is one
+//    shift and one add; mixed leaves (rare) read their row under a branch.
+//  * The majority test belongs to whole trees (t & 7 == 7, once it can
+//    succeed, and the last tree), so rf_pack flags those trees' leaves.  A
+//    lane that meets a flagged leaf parks on the PARK node, which links to
+//    itself, and remembers where to resume.  The wave serves its parked
+//    lanes together, in one PASS, once `pass_min` of them wait (or nothing
+//    else runs): majority test, label store for the rows that are decided,
+//    and the idle lanes take the next rows of the wave's range in lane
+//    order.  Per-row cost of the test and the refill is thus shared by many
+//    lanes, which matters because the kernel is bound by instruction issue.
+//
+// Termination: in a table rf_pack accepted every link points forward, so a
+// running lane reaches a flagged leaf within n_nodes steps and a pass
+// follows; the wave leaves when its range is used up and every lane is
+// idle.  Some lane runs in every iteration and a row's path is shorter than
+// n_nodes + 2, so a wave needs fewer than rows x (n_nodes + 2) iterations;
+// it gives up at that count, which bounds the loop for any other table
+// too, and no index past the table is ever loaded.
+//
+// Per row the arithmetic is the row-per-lane kernel's: trees in index
+// order, mixed leaves added to acc in that order, the majority test after
+// the same trees, first-maximum argmax — labels do not depend on which lane
+// ran a row or when.
+template <int C, bool LDS_NODES>
+__launch_bounds__(LDS_NODES ? 1024 : 256)
+__global__ void rf_predict_stream_kernel(const float* __restrict__ X,
+                                         const uint2* __restrict__ snodes,
+                                         const float* __restrict__ leaf_proba,
+                                         int* __restrict__ out, long long n,
+                                         int rows_per_wave, int n_nodes,
+                                         int n_leaves, int T, int pass_min) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* s_feat = reinterpret_cast<float*>(smem);
-  float* fA = s_feat + (int)threadIdx.x * 13;
-  float* fB = s_feat + (int)(blockDim.x + threadIdx.x) * 13;
+  uint2* s_nodes = reinterpret_cast<uint2*>(smem);
+  float* my_feat = reinterpret_cast<float*>(s_nodes + (LDS_NODES ? n_nodes + 2 : 0)) +
+                   (int)threadIdx.x * 13;
+  my_feat[12] = __uint_as_float(0x7fc00000u);  // NaN: leaves compare false
+  if (LDS_NODES) {
+    for (int i = threadIdx.x; i < n_nodes + 2; i += blockDim.x) s_nodes[i] = snodes[i];
+    __syncthreads();
+  }
 
-  long long stride = (long long)gridDim.x * blockDim.x * 2;
-  for (long long base = (long long)blockIdx.x * blockDim.x * 2; base < n;
-       base += stride) {
-    const long long rowA = base + threadIdx.x;
-    const long long rowB = base + blockDim.x + threadIdx.x;
-    if (rowA < n) {
-      Row12 x = load_row12(X, rowA);
+  const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const long long begin =
+      ((long long)blockIdx.x * (blockDim.x >> 6) + wave_in_block) * rows_per_wave;
+  if (begin >= n) return;  // wave-uniform
+  const long long left = n - begin;
+  const int count = left < (long long)rows_per_wave ? (int)left : rows_per_wave;
+  const float* __restrict__ Xw = X + begin * 12;
+  int* __restrict__ outw = out + begin;
+  const unsigned park = (unsigned)n_nodes + 1u;
+
+  // wave-uniform
+  int cursor = 0;  // next unassigned row of the range
+  int waiting = 0, trigger = 0;
+  long long budget = (long long)count * (n_nodes + 2);
+  // per lane; every lane starts idle: parked with nothing to resume
+  unsigned idx = park, resume = park;
+  int row = 0, t = 0;
+  float acc[C];
 #pragma unroll
-      for (int j = 0; j < 12; ++j) fA[j] = x.v[j];
-    }
-    if (rowB < n) {
-      Row12 x = load_row12(X, rowB);
+  for (int c = 0; c < C; ++c) acc[c] = 0.f;
+  unsigned long long votes = 0ull;  // 10-bit packed per-class pure counts
+
+  while (true) {
+    if (waiting >= trigger) {  // PASS: serve the parked lanes
+      if (idx == park && resume != park) {  // waits at a flagged leaf
+        float m1 = -INFINITY, m2 = -INFINITY;
+        int bi = 0;
 #pragma unroll
-      for (int j = 0; j < 12; ++j) fB[j] = x.v[j];
-    }
-    float accA[C], accB[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) accA[c] = accB[c] = 0.f;
-    unsigned long long votesA = 0ull, votesB = 0ull;
-    int decidedA = rowA >= n, decidedB = rowB >= n;
-    for (int t = 0; t < T; ++t) {
-      int idxA = roots[t], idxB = idxA;
-      bool runA = !decidedA, runB = !decidedB;
-      while (runA || runB) {
-        uint2 nodeA, nodeB;
-        if (runA) nodeA = nodes[idxA];
-        if (runB) nodeB = nodes[idxB];
-        if (runA) {
-          unsigned feat = nodeA.y & 0xffu;
-          if (feat >= 0xf0u) {
-            if (feat == 0xffu) {
-              int pr = (int)nodeA.x * C;
-#pragma unroll
-              for (int c = 0; c < C; ++c) accA[c] += leaf_proba[pr + c];
-            } else {
-              votesA += 1ull << ((feat & 0xfu) * 10);
-            }
-            runA = false;
-          } else {
-            float thr = __uint_as_float(nodeA.x);
-            idxA = (fA[feat] <= thr) ? idxA + 1 : (int)(nodeA.y >> 8);
-          }
+        for (int c = 0; c < C; ++c) {
+          // same values as the row-per-lane kernel's if/else-if, as selects
+          const float sc = acc[c] + vote_count(votes, c);
+          const bool lead = sc > m1;
+          m2 = lead ? m1 : (sc > m2 ? sc : m2);
+          m1 = lead ? sc : m1;
+          bi = lead ? c : bi;
         }
-        if (runB) {
-          unsigned feat = nodeB.y & 0xffu;
-          if (feat >= 0xf0u) {
-            if (feat == 0xffu) {
-              int pr = (int)nodeB.x * C;
-#pragma unroll
-              for (int c = 0; c < C; ++c) accB[c] += leaf_proba[pr + c];
-            } else {
-              votesB += 1ull << ((feat & 0xfu) * 10);
-            }
-            runB = false;
-          } else {
-            float thr = __uint_as_float(nodeB.x);
-            idxB = (fB[feat] <= thr) ? idxB + 1 : (int)(nodeB.y >> 8);
-          }
+        // t trees are done, T - t are left; a link to n_nodes ends the row
+        if (resume >= (unsigned)n_nodes || m1 - m2 > (float)(T - t)) {
+          outw[row] = bi;
+          resume = park;  // idle
+        } else {
+          idx = resume;
         }
       }
-      if ((t & 7) == 7) {
-        if (!decidedA) {
-          float m1 = -INFINITY, m2 = -INFINITY;
+      const unsigned long long idle = __ballot(idx == park);
+      int nidle = __popcll(idle);
+      if (cursor < count) {
+        // idle lanes take rows cursor, cursor+1, ... in lane order
+        const int r = cursor + (int)__builtin_amdgcn_mbcnt_hi(
+                                   (unsigned)(idle >> 32),
+                                   __builtin_amdgcn_mbcnt_lo((unsigned)idle, 0u));
+        if (idx == park && r < count) {
+          Row12 x = load_row12(Xw, r);
 #pragma unroll
-          for (int c = 0; c < C; ++c) {
-            float sc = accA[c] + (float)((votesA >> (c * 10)) & 1023ull);
-            if (sc > m1) { m2 = m1; m1 = sc; }
-            else if (sc > m2) m2 = sc;
-          }
-          if (m1 - m2 > (float)(T - 1 - t)) decidedA = 1;
+          for (int j = 0; j < 12; ++j) my_feat[j] = x.v[j];
+#pragma unroll
+          for (int c = 0; c < C; ++c) acc[c] = 0.f;
+          votes = 0ull;
+          row = r;
+          t = 0;
+          idx = 0;
         }
-        if (!decidedB) {
-          float m1 = -INFINITY, m2 = -INFINITY;
+        const int take = min(nidle, count - cursor);
+        cursor += take;
+        nidle -= take;
+      }
+      if (nidle == WAVE) break;  // range used up and every lane idle
+      // lanes still idle stay so; the next pass is due when pass_min lanes
+      // wait, or all that still run
+      trigger = min(pass_min, WAVE - nidle);
+      waiting = 0;
+    }
+    if (--budget < 0) break;  // not a table rf_pack made
+
+    const uint2 node = LDS_NODES ? s_nodes[idx] : snodes[idx];
+    const unsigned byte = node.y & 0xffu;
+    const float fv = my_feat[min(byte, 12u)];
+    unsigned next = (fv <= __uint_as_float(node.x)) ? idx + 1u : node.y >> 8;
+    next = min(next, park);
+    if (byte >= 0x80u) {  // leaf (some lane is at one nearly every step)
+      votes += 1ull << (byte & 63u);
+      ++t;
+      if (node.x != 0u) {  // mixed leaf: row + 1 of its distribution
+        const int pr = (int)min(node.x - 1u, (unsigned)(n_leaves - 1)) * C;
 #pragma unroll
-          for (int c = 0; c < C; ++c) {
-            float sc = accB[c] + (float)((votesB >> (c * 10)) & 1023ull);
-            if (sc > m1) { m2 = m1; m1 = sc; }
-            else if (sc > m2) m2 = sc;
-          }
-          if (m1 - m2 > (float)(T - 1 - t)) decidedB = 1;
-        }
-        if (__all(decidedA && decidedB)) break;
+        for (int c = 0; c < C; ++c) acc[c] += leaf_proba[pr + c];
       }
     }
-    if (rowA < n) {
-      float best = -INFINITY;
-      int bi = 0;
-#pragma unroll
-      for (int c = 0; c < C; ++c) {
-        float sc = accA[c] + (float)((votesA >> (c * 10)) & 1023ull);
-        if (sc > best) { best = sc; bi = c; }
-      }
-      out[rowA] = bi;
-    }
-    if (rowB < n) {
-      float best = -INFINITY;
-      int bi = 0;
-#pragma unroll
-      for (int c = 0; c < C; ++c) {
-        float sc = accB[c] + (float)((votesB >> (c * 10)) & 1023ull);
-        if (sc > best) { best = sc; bi = c; }
-      }
-      out[rowB] = bi;
-    }
+    const bool flagged = byte >= 0xc0u;  // leaf of a tree the test follows
+    waiting += __popcll(__ballot(flagged));
+    resume = flagged ? next : resume;
+    idx = flagged ? park : next;
   }
 }
 
@@ -489,19 +522,50 @@ __launch_bounds__(256) __global__ void rf_predict_wave_kernel(
     int bi = 0;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-      float sc = acc[c] + (float)((votes >> (c * 10)) & 1023ull);
+      float sc = acc[c] + vote_count(votes, c);
       if (sc > best) { best = sc; bi = c; }
     }
     out[row] = bi;
   }
 }
 
+// Below this many rows the default stays with the row-per-lane kernel: the
+// streaming kernel runs one 1024-thread block per CU, each stages the node
+// table, and a wave wants many rows to refill from.  Measured crossover on
+// the reference forest: behind at 2M rows, level at 4M, +8% at 10M
+// (profiles/rf_predict_stream.md).
+#define RF_STREAM_MIN_ROWS 4000000
+
 extern "C" void launch_rf_predict(const float* X, const unsigned* nodes,
-                                  const int* roots, const float* leaf_proba,
+                                  const unsigned* snodes, const int* roots,
+                                  const float* leaf_proba,
                                   int* out, long long n, int n_nodes,
                                   int n_leaves, int T, int C,
                                   hipStream_t stream) {
-  if (n <= 131072) {  // wave-per-row fills the chip at serve batch sizes
+  // TCSDN_RF_MODE (read per launch) picks the large-batch kernel:
+  //   5  streaming kernel (lanes advance through trees and rows on their
+  //      own), node table staged in LDS, 1024-thread blocks — THE DEFAULT
+  //      from RF_STREAM_MIN_ROWS rows up when the table fits
+  //   4  streaming kernel, node table in L2, 256-thread blocks
+  //   2  row-per-lane, features in LDS (pitch 13, one ds_read per node),
+  //      node table in L2 — the default between the wave-per-row cutover
+  //      and RF_STREAM_MIN_ROWS, and for forests too big for mode 5
+  //   1  row-per-lane, features and nodes both in LDS (costs a block of
+  //      occupancy next to a big forest)
+  //   0  row-per-lane, features in registers (sel12 select tree), nodes in
+  //      LDS when they fit
+  // Set explicitly, 4 and 5 apply at every n (how the tests reach the
+  // streaming kernel with small inputs); 0..2 only above the cutover.
+  // Measured on the 100-tree reference forest, 10M rows: modes 0/1/2 =
+  // 2.09/2.12/2.60 Gflows/s (profiles/kernel_opt_r02.md), modes 4/5 against
+  // mode 2 in profiles/rf_predict_stream.md.
+  const size_t snode_bytes = (size_t)(n_nodes + 2) * sizeof(uint2);
+  const bool snodes_fit = snode_bytes + 1024 * 13 * sizeof(float) <= 160 * 1024;
+  const char* mode_env = getenv("TCSDN_RF_MODE");
+  int mode = mode_env ? atoi(mode_env)
+                      : (n >= RF_STREAM_MIN_ROWS && snodes_fit ? 5 : 2);
+  const bool force_stream = mode_env && (mode == 4 || mode == 5);
+  if (n <= 131072 && !force_stream) {  // wave-per-row fills the chip at serve batch sizes
     dim3 wgrid((unsigned)((n + 3) / 4));
 #define RFW_CASE(CV)                                                        \
   case CV:                                                                  \
@@ -516,40 +580,64 @@ extern "C" void launch_rf_predict(const float* X, const unsigned* nodes,
     }
 #undef RFW_CASE
   }
+  if ((mode == 4 || mode == 5) && n > 0 && n_nodes > 0 && n_leaves > 0 && T > 0) {
+    // One row range per resident wave: the drain tail, the last rows of a
+    // range running on a thinning wave, is then about one row in ~19 at
+    // 10M rows.  Below 64 rows per wave there is nothing to refill, so
+    // small batches get fewer waves instead.
+    // TCSDN_RF_STREAM_RANGE overrides the rows per wave, and
+    // TCSDN_RF_STREAM_REFILL the count of parked lanes that starts a pass.
+    // Mode 5 stages the node table in LDS beside the feature rows (one
+    // 1024-thread block per CU); a table too big for that runs as mode 4.
+    const bool lds_nodes = mode == 5 && snodes_fit;
+    const int sb = lds_nodes ? 1024 : 256;
+    const long long resident = 256ll * (lds_nodes ? 16 : 32);
+    long long range = (n + resident - 1) / resident;
+    if (const char* e = getenv("TCSDN_RF_STREAM_RANGE")) range = atoll(e);
+    if (range < WAVE) range = WAVE;
+    if (range > (1ll << 30)) range = 1ll << 30;
+    int refill = 16;
+    if (const char* e = getenv("TCSDN_RF_STREAM_REFILL")) refill = atoi(e);
+    if (refill < 1) refill = 1;
+    if (refill > WAVE) refill = WAVE;
+    const long long waves = (n + range - 1) / range;
+    dim3 sgrid((unsigned)((waves + sb / WAVE - 1) / (sb / WAVE)));
+    size_t slds = (size_t)sb * 13 * sizeof(float) + (lds_nodes ? snode_bytes : 0);
+#define RFS_LAUNCH(CV, LN)                                                   \
+  do {                                                                       \
+    if (LN) {                                                                \
+      static bool once = false;                                              \
+      if (!once) {                                                           \
+        hipFuncSetAttribute(                                                 \
+            reinterpret_cast<const void*>(&rf_predict_stream_kernel<CV, LN>),\
+            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);         \
+        once = true;                                                         \
+      }                                                                      \
+    }                                                                        \
+    hipLaunchKernelGGL((rf_predict_stream_kernel<CV, LN>), sgrid, dim3(sb),  \
+                       slds, stream, X,                                      \
+                       reinterpret_cast<const uint2*>(snodes), leaf_proba,   \
+                       out, n, (int)range, n_nodes, n_leaves, T, refill);    \
+  } while (0)
+#define RFS_CASE(CV)                                                         \
+  case CV:                                                                   \
+    if (lds_nodes) RFS_LAUNCH(CV, true);                                     \
+    else RFS_LAUNCH(CV, false);                                              \
+    return;
+    switch (C) {
+      RFS_CASE(2) RFS_CASE(3) RFS_CASE(4) RFS_CASE(5) RFS_CASE(6) RFS_CASE(7)
+      RFS_CASE(8) RFS_CASE(12) RFS_CASE(16)
+      default: break;
+    }
+#undef RFS_CASE
+#undef RFS_LAUNCH
+  }
+  if (mode < 0 || mode > 2) mode = 2;
   const int block = 512;
   // Occupancy first: with nodes-only LDS a 43 KB forest admits 3 blocks
   // (24 waves) per CU.  Leaf probabilities go to LDS only when everything
   // still fits the 3-block budget; big forests fall back to the
   // (L2-resident) global tables.
-  //
-  // Feature placement (TCSDN_RF_MODE, A/B'd on hardware — 100-tree
-  // reference forest, 10M rows: mode 0 = 2.09 Gflows/s, mode 1 = 2.12,
-  // mode 2 = 2.60): mode 0 keeps features in registers (sel12 select tree,
-  // nodes LDS when they fit); mode 1 also stages features in LDS (pitch 13,
-  // one ds_read per node) but loses a block of occupancy next to a big
-  // forest; mode 2 — THE DEFAULT — stages features in LDS and leaves the
-  // node table in L2 (42 KB forest ≪ 4 MB per-XCD L2; the ~200-cycle node
-  // fetch hides behind 32 waves/CU while the VALU sheds the ~10-op select
-  // tree this kernel was issue-bound on).
-  int mode = 2;
-  if (const char* e = getenv("TCSDN_RF_MODE")) mode = atoi(e);
-  if (mode == 3) {  // ILP-2: two chains per lane, 256-thread blocks
-    const int b2 = 256;
-    size_t lds2 = (size_t)b2 * 2 * 13 * sizeof(float);
-    dim3 g2(ts_grid((n + 1) / 2, b2, 4096));
-#define RFI_CASE(CV)                                                         \
-  case CV:                                                                   \
-    hipLaunchKernelGGL((rf_predict_ilp2_kernel<CV>), g2, dim3(b2), lds2,     \
-                       stream, X, reinterpret_cast<const uint2*>(nodes),     \
-                       roots, leaf_proba, out, n, T);                        \
-    return;
-    switch (C) {
-      RFI_CASE(2) RFI_CASE(3) RFI_CASE(4) RFI_CASE(5) RFI_CASE(6) RFI_CASE(7)
-      RFI_CASE(8) RFI_CASE(12) RFI_CASE(16)
-      default: break;
-    }
-#undef RFI_CASE
-  }
   size_t node_bytes = (size_t)n_nodes * sizeof(uint2);
   size_t prob_bytes = (size_t)n_leaves * C * sizeof(float);
   size_t feat_bytes = (size_t)block * 13 * sizeof(float);

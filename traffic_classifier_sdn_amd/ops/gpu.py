@@ -211,13 +211,42 @@ def rf_hist(bins: torch.Tensor, y: torch.Tensor, nid: torch.Tensor, n_nodes: int
 
 def rf_pack(forest: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
     """Pack the SoA forest (ops.cpu.rf_flatten layout) into the traversal
-    kernel's uint2 node format:
+    kernels' uint2 node tables.
+
+    ``nodes`` (row-per-lane and wave-per-row kernels), n_nodes entries:
       word0 = f32 threshold bits (inner) | leaf-probability row (mixed leaf)
       word1 = (right_child_GLOBAL << 8) | feature byte
     Feature byte: 0..0xef = inner-node feature id; 0xf0|class = PURE leaf
-    (one-hot distribution, counted in-register by the kernel); 0xff = mixed
-    leaf (distribution row in word0).  Forests up to 1023 trees and 16
-    classes; features up to 0xef.
+    (one-hot distribution, counted in-register by the kernels); 0xff = mixed
+    leaf (distribution row in word0).
+
+    ``snodes`` (streaming kernel), n_nodes + 2 entries:
+      word0 = f32 threshold bits (inner) | 0 (pure leaf) |
+              leaf-probability row + 1 (mixed leaf)
+      word1 = (link_GLOBAL << 8) | byte
+    The link is the right child for an inner node and the NEXT TREE'S ROOT
+    for a leaf; after the last tree it is ``n_nodes``, the terminal value.
+    Byte: 0..0x7f = inner-node feature id; 0x80 | flag << 6 | shift = leaf,
+    where shift is 10 * class for a pure leaf, 61 for a mixed one and 60 for
+    neither (the kernel adds 1 << shift to its packed vote register, whose
+    bits 60..63 belong to no class), and flag marks the leaves of the trees
+    after which the kernel runs its majority test: t & 7 == 7 once
+    2t + 2 >= T (before that leader - runner-up <= t + 1 cannot exceed the
+    T - 1 - t trees left), and the last tree.  Entry n_nodes is a flagged
+    leaf linked to itself, which ends any row that gets there; entry
+    n_nodes + 1 is the PARK node the kernel's idle lanes spin on: an inner
+    node with feature id 12 (no such feature: the kernel's slot 12 holds
+    NaN, so the step goes right) whose right child is itself.
+
+    The kernels count pure leaves in 10-bit fields of one 64-bit register,
+    which holds 6 classes and 1023 trees; a forest beyond either gets no
+    pure leaves in either table.
+
+    The streaming kernel walks one strictly increasing chain of node
+    indices per row, from the first root to the terminal value, so the
+    order is checked here: ``ValueError`` unless every right child lies
+    after its parent inside the same tree and every next-root after its
+    leaf.
     """
     thr = forest["threshold"].cpu()
     right = forest["right"].cpu().to(torch.int64)
@@ -226,29 +255,56 @@ def rf_pack(forest: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
     offsets = forest["tree_offset"].cpu().to(torch.int64)
     n_nodes = thr.numel()
     n_trees = offsets.numel() - 1
-    base = torch.repeat_interleave(offsets[:-1], offsets[1:] - offsets[:-1])
+    n_classes = int(forest["n_classes"])
+    counts = offsets[1:] - offsets[:-1]
+    if int(offsets[0]) != 0 or int(offsets[-1]) != n_nodes or bool((counts < 1).any()):
+        raise ValueError("tree_offset must rise from 0 to n_nodes, one or more nodes per tree")
+    if n_nodes + 2 >= 1 << 24:
+        raise ValueError("packed node format holds at most 2^24 - 3 nodes")
+    base = torch.repeat_interleave(offsets[:-1], counts)
+    next_root = torch.repeat_interleave(offsets[1:], counts)
+    tree = torch.repeat_interleave(torch.arange(n_trees, dtype=torch.int64), counts)
+    index = torch.arange(n_nodes, dtype=torch.int64)
     is_leaf = feat < 0
+    if bool((feat[~is_leaf] > 0x7F).any()):
+        raise ValueError("feature ids above 0x7f do not fit the packed node")
+    right_global = right + base
+    inner_ok = (right_global > index) & (right_global < next_root)
+    if not bool(inner_ok[~is_leaf].all()):
+        raise ValueError("right child must lie after its parent, inside the same tree")
+    if not bool((next_root > index).all()) or (n_nodes and int(next_root[-1]) != n_nodes):
+        raise ValueError("next-root chain must increase and end at n_nodes")
     probs = forest["leaf_proba"].cpu()
     # pure leaf: exactly one class carries the whole mass
     pmax, pcls = probs.max(dim=1)
     leaf_pure = torch.zeros_like(is_leaf)
     leaf_cls = torch.zeros_like(feat)
     valid = leaf_index >= 0
-    leaf_pure[valid] = pmax[leaf_index[valid]] >= 1.0
+    if n_classes * 10 <= 64 and n_trees <= 1023:  # else the vote fields overflow
+        leaf_pure[valid] = pmax[leaf_index[valid]] >= 1.0
     leaf_cls[valid] = pcls[leaf_index[valid]].to(torch.int64)
-    w0 = torch.where(
-        is_leaf, leaf_index.to(torch.int32), thr.view(torch.int32)
-    ).to(torch.int32)
-    right_global = (right + base) << 8
+    thr_bits = thr.view(torch.int32).to(torch.int64)
+    w0 = torch.where(is_leaf, leaf_index, thr_bits).to(torch.int32)
     leaf_byte = torch.where(leaf_pure, 0xF0 | leaf_cls, torch.tensor(0xFF, dtype=torch.int64))
-    w1 = torch.where(is_leaf, leaf_byte, right_global | feat).to(torch.int32)
+    w1 = torch.where(is_leaf, leaf_byte, (right_global << 8) | feat).to(torch.int32)
     nodes = torch.stack([w0, w1], dim=1).contiguous()
+
+    tested = (((tree & 7) == 7) & (2 * tree + 2 >= n_trees)) | (tree == n_trees - 1)
+    shift = torch.where(leaf_pure, 10 * leaf_cls, torch.tensor(61, dtype=torch.int64))
+    s_byte = 0x80 | (tested.to(torch.int64) << 6) | shift
+    zero = torch.zeros_like(leaf_index)
+    s0 = torch.where(is_leaf, torch.where(leaf_pure, zero, leaf_index + 1), thr_bits)
+    s1 = torch.where(is_leaf, (next_root << 8) | s_byte, (right_global << 8) | feat)
+    end = torch.tensor([[0, (n_nodes << 8) | 0x80 | 0x40 | 60]], dtype=torch.int64)
+    park = torch.tensor([[0, ((n_nodes + 1) << 8) | 12]], dtype=torch.int64)
+    snodes = torch.cat([torch.stack([s0, s1], dim=1), end, park]).to(torch.int32).contiguous()
     return {
         "nodes": nodes.to(device),
+        "snodes": snodes.to(device),
         "roots": offsets[:-1].to(torch.int32).to(device),
         "leaf_proba": forest["leaf_proba"].to(torch.float32).to(device).contiguous(),
         "n_leaves": int(forest["leaf_proba"].shape[0]),
-        "n_classes": int(forest["n_classes"]),
+        "n_classes": n_classes,
     }
 
 
@@ -260,6 +316,7 @@ def rf_argmax(X: torch.Tensor, forest: Dict[str, torch.Tensor]) -> torch.Tensor:
     return _ext.rf_predict(
         _f32(X),
         packed["nodes"],
+        packed["snodes"],
         packed["roots"],
         packed["leaf_proba"],
         packed["n_leaves"],
