@@ -39,6 +39,15 @@ def main():
 
     rf = load_model(os.path.join(MODELS, "RandomForestClassifier.npz"), device="cuda")
     out["rf_predict"] = timeit(lambda: og.rf_argmax(X, rf.forest))
+    # class scores (all trees, no early exit) beside the argmax kernel at the
+    # same shapes: serve batch (wave-per-row) and 1M rows (row-per-lane)
+    X8k, X1m = X[:8192], X[: min(n, 1_000_000)]
+    out["rf_predict@8192"] = timeit(lambda: og.rf_argmax(X8k, rf.forest), steps=50)
+    out["rf_scores@8192"] = timeit(
+        lambda: og.rf_predict_scores(X8k, rf.forest, want_proba=False), steps=50)
+    out["rf_predict@1M"] = timeit(lambda: og.rf_argmax(X1m, rf.forest))
+    out["rf_scores@1M"] = timeit(lambda: og.rf_predict_scores(X1m, rf.forest, want_proba=False))
+    out["rf_proba@1M"] = timeit(lambda: og.rf_predict_proba(X1m, rf.forest))
 
     gnb = load_model(os.path.join(MODELS, "GaussianNB.npz"), device="cuda")
     th = gnb.theta_.float().cuda()
@@ -80,7 +89,8 @@ def main():
 
     rows = {"n_rows": n}
     for k, v in out.items():
-        base = 1_000_000 if "@1M" in k else (2_000_000 if "@2M" in k else n)
+        base = (1_000_000 if "@1M" in k else 2_000_000 if "@2M" in k
+                else 8192 if "@8192" in k else n)
         rows[k] = {"ms": v * 1e3, "rows_per_s": base / v}
     print(json.dumps(rows, indent=1))
 

@@ -98,6 +98,10 @@ def main(argv: Optional[list] = None) -> int:
                         help="expose serve metrics on a Prometheus scrape port")
     parser.add_argument("--stats", action="store_true",
                         help="emit one JSON perf line (flows, predict_ms, flows/sec) per prediction pass on stderr")
+    parser.add_argument("--confidence", action="store_true",
+                        help="append a Confidence column (top class probability) to the table")
+    parser.add_argument("--min-confidence", type=float, default=0.0, metavar="P",
+                        help="show flows whose confidence is below P as 'unknown' (implies --confidence)")
     args = parser.parse_args(argv)
 
     if args.subcommand == "train":
@@ -134,7 +138,15 @@ def main(argv: Optional[list] = None) -> int:
         print(f"ERROR: checkpoint {path} not found", file=sys.stderr)
         return 2
     model = load_model(path, device=args.device)
-    rc = RealtimeClassifier(model, stats=args.stats, prometheus_port=args.prometheus)
+    confidence = args.confidence or args.min_confidence > 0.0
+    if confidence and not hasattr(model, "predict_proba"):
+        print(f"ERROR: {args.subcommand} has no class probabilities: no --confidence",
+              file=sys.stderr)
+        return 2
+    # the streams as they are now, not as they were when serve was imported
+    rc = RealtimeClassifier(model, out=sys.stdout, stats=args.stats, stats_out=sys.stderr,
+                            prometheus_port=args.prometheus,
+                            confidence=confidence, min_confidence=args.min_confidence)
     try:
         rc.run(_line_source(args))
     except KeyboardInterrupt:

@@ -30,6 +30,8 @@ void launch_kmeans_assign(const float*, const float*, int*, double*, double*,
 void launch_rf_predict(const float*, const unsigned*, const unsigned*,
                        const int*, const float*, int*, long long, int, int,
                        int, int, hipStream_t);
+int launch_rf_scores(const float*, const unsigned*, const int*, const float*,
+                     float*, int*, float*, long long, int, int, hipStream_t);
 void launch_svc_predict(const float*, const float*, const float*,
                         const unsigned char*, const float*, int*, long long,
                         int, int, float, hipStream_t);
@@ -159,6 +161,37 @@ static torch::Tensor rf_predict(torch::Tensor X, torch::Tensor nodes,
                     out.data_ptr<int>(), n, n_nodes, (int)n_leaves, T, (int)C,
                     cur_stream());
   return out;
+}
+
+// Class scores of the forest (rf_proba_kernels.hip): every tree counts.
+// Returns (proba [n,C] f32 or an empty tensor, labels [n] i32, conf [n] f32).
+static std::vector<torch::Tensor> rf_predict_scores(
+    torch::Tensor X, torch::Tensor nodes, torch::Tensor roots,
+    torch::Tensor leaf_proba, int64_t n_leaves, int64_t C, bool want_proba) {
+  CHECK_IN(X, torch::kFloat32);
+  CHECK_IN(nodes, torch::kInt32);  // packed uint2 as 2x int32
+  CHECK_IN(roots, torch::kInt32);
+  CHECK_IN(leaf_proba, torch::kFloat32);
+  TORCH_CHECK(X.dim() == 2 && X.size(1) == 12, "X must be (n,12)");
+  TORCH_CHECK(nodes.dim() == 2 && nodes.size(1) == 2,
+              "nodes must be (n_nodes,2) int32");
+  TORCH_CHECK(C >= 2 && C <= 8, "rf_predict_scores supports 2..8 classes, got ", C);
+  TORCH_CHECK(n_leaves >= 0 && leaf_proba.numel() >= n_leaves * C,
+              "leaf_proba must hold n_leaves rows of C");
+  const long long n = X.size(0);
+  const int T = roots.size(0);
+  TORCH_CHECK(T >= 1, "forest has no trees");
+  auto proba = torch::empty({want_proba ? n : 0, C}, X.options());
+  auto labels = torch::empty({n}, X.options().dtype(torch::kInt32));
+  auto conf = torch::empty({n}, X.options());
+  const int rc = launch_rf_scores(
+      X.data_ptr<float>(),
+      reinterpret_cast<const unsigned*>(nodes.data_ptr<int>()),
+      roots.data_ptr<int>(), leaf_proba.data_ptr<float>(),
+      want_proba ? proba.data_ptr<float>() : nullptr, labels.data_ptr<int>(),
+      conf.data_ptr<float>(), n, T, (int)C, cur_stream());
+  TORCH_CHECK(rc == 0, "rf_predict_scores: no kernel for ", C, " classes");
+  return {proba, labels, conf};
 }
 
 static torch::Tensor svc_predict(torch::Tensor X, torch::Tensor SV,
@@ -520,6 +553,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_argmax", &linear_argmax, "logits+argmax");
   m.def("kmeans_assign", &kmeans_assign, "Lloyd assign + partial update");
   m.def("rf_predict", &rf_predict, "packed-forest traversal + vote");
+  m.def("rf_predict_scores", &rf_predict_scores,
+        "packed-forest traversal, all trees: (proba | empty, labels, conf)");
   m.def("svc_predict", &svc_predict, "RBF Gram + OVO vote");
   m.def("knn_topk", &knn_topk, "brute-force top-k (+fused vote)");
   m.def("knn_topk_mfma", &knn_topk_mfma, "MFMA distance-GEMM top-k (+fused vote)",

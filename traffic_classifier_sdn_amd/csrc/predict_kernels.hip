@@ -196,33 +196,6 @@ extern "C" void launch_kmeans_assign(const float* X, const float* centers,
 // give 3 blocks = 24 waves per CU.
 // ---------------------------------------------------------------------------
 
-// select v[f] for runtime f in [0,12) with compile-time register indices:
-// two levels — pick r = f&3 within each quad, then the quad q = f>>2.
-DEV float sel12(const Row12& x, unsigned f) {
-  unsigned r = f & 3u, q = f >> 2;
-  float a = (r & 1u) ? x.v[1] : x.v[0];
-  float b = (r & 2u) ? ((r & 1u) ? x.v[3] : x.v[2]) : a;
-  float q0 = b;
-  float c = (r & 1u) ? x.v[5] : x.v[4];
-  float d = (r & 2u) ? ((r & 1u) ? x.v[7] : x.v[6]) : c;
-  float q1 = d;
-  float e = (r & 1u) ? x.v[9] : x.v[8];
-  float g = (r & 2u) ? ((r & 1u) ? x.v[11] : x.v[10]) : e;
-  float q2 = g;
-  float lo = (q & 1u) ? q1 : q0;
-  return (q & 2u) ? q2 : lo;
-}
-
-// Pure-leaf votes of class c out of the packed register (10 bits per class).
-// Only classes 0..5 have a field: rf_pack gives a forest with more classes
-// no pure leaves, and a shift past bit 63 must not even be formed (c is a
-// compile-time constant in every caller's unrolled loop).  The u32 cast
-// keeps the convert a single instruction.
-DEV float vote_count(unsigned long long votes, int c) {
-  return c * 10 + 10 <= 64 ? (float)(unsigned)((votes >> (c * 10)) & 1023ull)
-                           : 0.f;
-}
-
 // Traversal body shared by the four table-placement variants.  LDS_NODES /
 // LDS_PROBS are compile-time so the node fetch lowers to ds_read_b64 (LDS)
 // or global_load_dwordx2 — a runtime ternary over the two pointers would

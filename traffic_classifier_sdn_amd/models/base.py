@@ -58,6 +58,22 @@ class Estimator:
         """Integer class-index predictions (device tensor)."""
         raise NotImplementedError
 
+    def predict_with_confidence(self, X: ArrayLike):
+        """(labels, conf): ``predict(X)`` and, per row, the largest class
+        probability as float32.  The labels are always ``predict``'s, so
+        asking for confidence never changes one.  Models without
+        ``predict_proba`` raise NotImplementedError."""
+        proba_fn = getattr(self, "predict_proba", None)
+        if proba_fn is None:
+            raise NotImplementedError(
+                f"{type(self).__name__} has no class probabilities to take a confidence from"
+            )
+        labels = self.predict(X)
+        proba = proba_fn(X)
+        if isinstance(proba, torch.Tensor):
+            proba = proba.cpu().numpy()
+        return labels, np.asarray(proba).max(axis=1).astype(np.float32)
+
     def to(self, device: str):
         self.device = torch.device(device)
         for name, val in list(self.__dict__.items()):

@@ -224,6 +224,26 @@ class RandomForestClassifier(Estimator):
         Xt = as_tensor(X, self.device, torch.float32)
         return ops.rf_predict_proba(Xt, self.forest)
 
+    def predict_log_proba(self, X: ArrayLike) -> torch.Tensor:
+        """log of predict_proba; -inf where no tree votes for a class
+        (sklearn API)."""
+        return torch.log(self.predict_proba(X))
+
+    def predict_index_conf(self, X: ArrayLike):
+        """(idx int32[n], conf float32[n]) device tensors from one pass over
+        all trees: the class index and its probability, without storing the
+        probability matrix.  idx is the first-maximum argmax of the class
+        sums, the rule of predict_index."""
+        Xt = as_tensor(X, self.device, torch.float32)
+        _, idx, conf = ops.rf_predict_scores(Xt, self.forest, want_proba=False)
+        return idx, conf
+
+    def predict_with_confidence(self, X: ArrayLike):
+        idx, conf = self.predict_index_conf(X)
+        idx = idx.cpu().numpy()
+        labels = idx if self.classes_ is None else self.classes_[idx]
+        return labels, conf.cpu().numpy().astype(np.float32)
+
     # -- checkpointing -------------------------------------------------
     def to_params(self) -> Dict[str, Any]:
         return {

@@ -341,6 +341,19 @@ def rf_argmax(X: torch.Tensor, forest: Dict[str, torch.Tensor]) -> torch.Tensor:
     return torch.argmax(rf_predict_proba(X, forest), dim=1).to(torch.int32)
 
 
+def rf_predict_scores(
+    X: torch.Tensor, forest: Dict[str, torch.Tensor], want_proba: bool = True
+) -> Tuple[Optional[torch.Tensor], torch.Tensor, torch.Tensor]:
+    """(proba[n,C] f32, labels[n] int32, conf[n] f32): the class
+    probabilities, their first-maximum argmax and the top probability (CPU
+    oracle of the HIP scores kernels).  ``want_proba=False`` returns None in
+    place of proba."""
+    proba = rf_predict_proba(X, forest)
+    labels = torch.argmax(proba, dim=1).to(torch.int32)
+    conf = proba.max(dim=1).values
+    return (proba if want_proba else None), labels, conf
+
+
 # ----------------------------------------------------------------------
 # Serve-path feature extraction (CPU oracle of the GPU kernel; mirrors the
 # reference Flow update math, traffic_classifier.py:63-96)

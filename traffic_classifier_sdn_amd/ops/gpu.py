@@ -308,11 +308,17 @@ def rf_pack(forest: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
     }
 
 
-def rf_argmax(X: torch.Tensor, forest: Dict[str, torch.Tensor]) -> torch.Tensor:
+def _rf_packed(X: torch.Tensor, forest: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The forest's packed tables on X's device, cached in the forest dict."""
     packed = forest.get("_packed")
     if packed is None or packed["nodes"].device != X.device:
         packed = rf_pack(forest, X.device)
         forest["_packed"] = packed
+    return packed
+
+
+def rf_argmax(X: torch.Tensor, forest: Dict[str, torch.Tensor]) -> torch.Tensor:
+    packed = _rf_packed(X, forest)
     return _ext.rf_predict(
         _f32(X),
         packed["nodes"],
@@ -322,6 +328,34 @@ def rf_argmax(X: torch.Tensor, forest: Dict[str, torch.Tensor]) -> torch.Tensor:
         packed["n_leaves"],
         packed["n_classes"],
     )
+
+
+def rf_predict_scores(
+    X: torch.Tensor, forest: Dict[str, torch.Tensor], want_proba: bool = True
+) -> Tuple[Optional[torch.Tensor], torch.Tensor, torch.Tensor]:
+    """(proba[n,C] f32 | None, labels[n] int32, conf[n] f32) from the scores
+    kernels (csrc/rf_proba_kernels.hip): every tree counts, labels are the
+    first-maximum argmax of the class sums and conf is the top probability.
+    ``want_proba=False`` skips the proba store (the serve path)."""
+    if X.shape[1] != 12:
+        return _cpu.rf_predict_scores(X, forest, want_proba)
+    packed = _rf_packed(X, forest)
+    if not 2 <= packed["n_classes"] <= 8:  # the kernels' class range
+        return _cpu.rf_predict_scores(X, forest, want_proba)
+    proba, labels, conf = _ext.rf_predict_scores(
+        _f32(X),
+        packed["nodes"],
+        packed["roots"],
+        packed["leaf_proba"],
+        packed["n_leaves"],
+        packed["n_classes"],
+        want_proba,
+    )
+    return (proba if want_proba else None), labels, conf
+
+
+def rf_predict_proba(X: torch.Tensor, forest: Dict[str, torch.Tensor]) -> torch.Tensor:
+    return rf_predict_scores(X, forest)[0]
 
 
 # ----------------------------------------------------------------------
@@ -366,7 +400,3 @@ def kmeans_labels(X: torch.Tensor, centers: torch.Tensor) -> torch.Tensor:
         return _cpu.kmeans_labels(X, centers)
     labels, _, _, _ = _ext.kmeans_assign(_f32(X), _f32_cached(centers), False)
     return labels
-
-
-# diagnostic-only path (torch eager; not benched)
-rf_predict_proba = _cpu.rf_predict_proba

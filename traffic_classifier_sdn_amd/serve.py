@@ -27,13 +27,20 @@ from .utils.schema import CLASS_NAMES, CSV_HEADER
 from .utils.table import Table
 
 
-def render_flow_table(table: FlowTable, labels) -> str:
-    """The reference's console table (traffic_classifier.py:100-118)."""
-    t = Table(["Flow ID", "Src MAC", "Dest MAC", "Traffic Type", "Forward Status", "Reverse Status"])
+def render_flow_table(table: FlowTable, labels, confidence=None) -> str:
+    """The reference's console table (traffic_classifier.py:100-118); with
+    ``confidence`` (one value per flow) a last column shows it."""
+    cols = ["Flow ID", "Src MAC", "Dest MAC", "Traffic Type", "Forward Status", "Reverse Status"]
+    if confidence is not None:
+        cols.append("Confidence")
+    t = Table(cols)
     metas = table.metas()
     statuses = table.statuses()
     for i, (meta, (fs, rs)) in enumerate(zip(metas, statuses)):
-        t.add_row([i, meta.ethsrc, meta.ethdst, labels[i], fs, rs])
+        row = [i, meta.ethsrc, meta.ethdst, labels[i], fs, rs]
+        if confidence is not None:
+            row.append("%.2f" % confidence[i])
+        t.add_row(row)
     return str(t)
 
 
@@ -60,8 +67,15 @@ class RealtimeClassifier:
         stats: bool = False,
         stats_out: TextIO = sys.stderr,
         prometheus_port: int = 0,
+        confidence: bool = False,
+        min_confidence: float = 0.0,
     ) -> None:
         self.model = model
+        # per-flow confidence column; a flow below min_confidence (which
+        # implies the column) is shown as "unknown"
+        self.min_confidence = float(min_confidence)
+        self.confidence = bool(confidence) or self.min_confidence > 0.0
+        self.last_confidence = None  # float32[n] of the last pass
         self.parser = PollStreamParser()
         self.predict_every = predict_every
         self.out = out
@@ -77,8 +91,16 @@ class RealtimeClassifier:
     def classify_now(self) -> np.ndarray:
         table = self.parser.table
         if len(table) == 0:
+            if self.confidence:
+                self.last_confidence = np.zeros(0, dtype=np.float32)
             return np.asarray([], dtype=object)
         X = table.feature_matrix(dtype=np.float32)
+        if self.confidence:
+            pred, conf = self.model.predict_with_confidence(X)
+            self.last_confidence = conf
+            pred = np.asarray(pred, dtype=object)
+            pred[conf < self.min_confidence] = "unknown"
+            return pred
         pred = self.model.predict(X)
         if self.model.classes_ is None:  # unsupervised: cluster ids -> names
             names = getattr(self.model, "cluster_label_names_", None)
@@ -107,7 +129,8 @@ class RealtimeClassifier:
             t0 = time.perf_counter()
             labels = self.classify_now()
             predict_s = time.perf_counter() - t0
-            self.out.write(render_flow_table(self.parser.table, labels) + "\n")
+            conf = self.last_confidence if self.confidence else None
+            self.out.write(render_flow_table(self.parser.table, labels, conf) + "\n")
             self.out.flush()
             if self.prom is not None:
                 self.prom.observe_pass(
@@ -115,18 +138,17 @@ class RealtimeClassifier:
                 )
             if self.stats:
                 n = len(self.parser.table)
-                self.stats_out.write(
-                    json.dumps(
-                        {
-                            "flows": n,
-                            "records": self.parser.records,
-                            "predict_ms": predict_s * 1e3,
-                            "flows_per_sec": n / predict_s if predict_s > 0 else None,
-                            "device": str(getattr(self.model, "device", "cpu")),
-                        }
-                    )
-                    + "\n"
-                )
+                line = {
+                    "flows": n,
+                    "records": self.parser.records,
+                    "predict_ms": predict_s * 1e3,
+                    "flows_per_sec": n / predict_s if predict_s > 0 else None,
+                    "device": str(getattr(self.model, "device", "cpu")),
+                }
+                if conf is not None:
+                    line["mean_confidence"] = float(conf.mean()) if n else None
+                    line["unknown"] = int((conf < self.min_confidence).sum())
+                self.stats_out.write(json.dumps(line) + "\n")
                 self.stats_out.flush()
             return True
         return False

@@ -30,6 +30,7 @@ class GpuServeEngine:
         capacity: int = 8192,
         use_graph: bool = True,
         device: str = "cuda",
+        confidence: bool = False,
     ) -> None:
         self.models = models
         self.capacity = capacity
@@ -45,6 +46,15 @@ class GpuServeEngine:
         self.d_times = torch.zeros(capacity, 6, dtype=torch.float64, device=self.device)
         self.d_labels: Dict[str, torch.Tensor] = {}
         self.h_labels: Dict[str, torch.Tensor] = {}
+        # per-flow confidence (top class probability) of the models that have
+        # predict_index_conf; their labels then come from that same call
+        self._conf_models = (
+            [n for n, m in models.items() if hasattr(m, "predict_index_conf")]
+            if confidence else []
+        )
+        self.d_conf: Dict[str, torch.Tensor] = {}
+        self.h_conf: Dict[str, torch.Tensor] = {}
+        self.confidence: Dict[str, np.ndarray] = {}
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self.last_latency_s = 0.0
 
@@ -53,14 +63,23 @@ class GpuServeEngine:
         from . import ops
 
         X = ops.flow_features(self.d_cur, self.d_prev, self.d_times)
+        pin = self.device.type == "cuda"
         for name, model in self.models.items():
-            labels = model.predict_index(X)
+            if name in self._conf_models:
+                labels, conf = model.predict_index_conf(X)
+                if name in self.d_conf:
+                    self.d_conf[name].copy_(conf)
+                else:
+                    self.d_conf[name] = conf
+                    self.h_conf[name] = torch.empty_like(conf, device="cpu", pin_memory=pin)
+            else:
+                labels = model.predict_index(X)
             if name in self.d_labels:
                 self.d_labels[name].copy_(labels)
             else:
                 self.d_labels[name] = labels
                 self.h_labels[name] = torch.empty_like(
-                    labels, device="cpu", pin_memory=self.device.type == "cuda"
+                    labels, device="cpu", pin_memory=pin
                 )
 
     def _capture(self) -> None:
@@ -79,7 +98,9 @@ class GpuServeEngine:
     # -- per-poll entry -------------------------------------------------
     def classify(self, table: FlowTable) -> Dict[str, np.ndarray]:
         """Run one classification pass over every live flow; returns
-        {model_name: labels[n] int32} (class indices)."""
+        {model_name: labels[n] int32} (class indices).  With
+        ``confidence=True`` the pass also leaves {model_name: float32[n]} in
+        ``self.confidence`` for the models that support it."""
         n = len(table)
         t0 = time.perf_counter()
         if n > self.capacity:
@@ -101,15 +122,23 @@ class GpuServeEngine:
             out = {}
             for name in self.models:
                 self.h_labels[name].copy_(self.d_labels[name], non_blocking=True)
+            for name in self._conf_models:
+                self.h_conf[name].copy_(self.d_conf[name], non_blocking=True)
             torch.cuda.synchronize()
             for name in self.models:
                 out[name] = self.h_labels[name][:n].numpy().copy()
+            self.confidence = {
+                name: self.h_conf[name][:n].numpy().copy() for name in self._conf_models
+            }
         else:
             self.d_cur.copy_(self.h_cur)
             self.d_prev.copy_(self.h_prev)
             self.d_times.copy_(self.h_times)
             self._compute()
             out = {name: self.d_labels[name][:n].numpy().copy() for name in self.models}
+            self.confidence = {
+                name: self.d_conf[name][:n].numpy().copy() for name in self._conf_models
+            }
         self.last_latency_s = time.perf_counter() - t0
         return out
 
@@ -121,7 +150,13 @@ class GpuServeEngine:
         to = lambda a: torch.from_numpy(a).to(self.device)
         X = ops.flow_features(to(cur), to(prev), to(times))
         out = {}
+        self.confidence = {}
         for name, model in self.models.items():
-            out[name] = model.predict_index(X).cpu().numpy()
+            if name in self._conf_models:
+                labels, conf = model.predict_index_conf(X)
+                self.confidence[name] = conf.cpu().numpy()
+            else:
+                labels = model.predict_index(X)
+            out[name] = labels.cpu().numpy()
         self.last_latency_s = time.perf_counter() - t0
         return out
