@@ -3,11 +3,13 @@
 
     python -m traffic_classifier_sdn_amd train <TypeOfData> [--source ...]
     python -m traffic_classifier_sdn_amd <algo>              [--source ...]
+    python -m traffic_classifier_sdn_amd ensemble [--members a,b,...] [--weights ...]
 
 Subcommands: train, logistic, kmeans, knearest, svm, Randomforest,
 gaussiannb (SUBCOMMANDS at traffic_classifier.py:189; the reference's
 unreachable-`knearest` loader bug, SURVEY.md §2.1, is fixed: `knearest`
-loads the KNeighbors checkpoint).
+loads the KNeighbors checkpoint).  `ensemble` is new here: a soft vote over
+the class probabilities of several checkpoints (models/ensemble.py).
 
 Telemetry sources:
   --source subprocess   spawn a monitor command (default: the in-package
@@ -26,7 +28,9 @@ import subprocess
 import sys
 from typing import Iterable, Optional
 
-SUBCOMMANDS = ("train", "logistic", "kmeans", "knearest", "svm", "Randomforest", "gaussiannb")
+SUBCOMMANDS = ("train", "logistic", "kmeans", "knearest", "svm", "Randomforest", "gaussiannb",
+               "ensemble")
+DEFAULT_MEMBERS = "Randomforest,gaussiannb,logistic,knearest"
 
 DEFAULT_TIMEOUT = 15 * 60  # training-collection window (traffic_classifier.py:27)
 
@@ -79,6 +83,32 @@ def _checkpoint_path(algo: str, models_dir: str) -> str:
     return os.path.join(models_dir, fname)
 
 
+def _load_ensemble(args):
+    """The `ensemble` subcommand's model, or None after one line on stderr
+    (unknown or missing member, member without probabilities, bad weights)."""
+    from .models import ALGO_TO_CHECKPOINT, SoftVoteEnsemble, load_model
+
+    names = [m.strip() for m in args.members.split(",") if m.strip()]
+    try:
+        weights = None
+        if args.weights is not None:
+            weights = [float(w) for w in args.weights.split(",")]
+        members = {}
+        for name in names:
+            if name not in ALGO_TO_CHECKPOINT:
+                raise ValueError(f"unknown ensemble member {name!r}")
+            if name in members:
+                raise ValueError(f"ensemble member {name!r} is named twice")
+            path = _checkpoint_path(name, args.models_dir)
+            if not os.path.exists(path):
+                raise ValueError(f"checkpoint {path} not found")
+            members[name] = load_model(path, device=args.device)
+        return SoftVoteEnsemble(members, weights)
+    except ValueError as e:
+        print(f"ERROR: {e}", file=sys.stderr)
+        return None
+
+
 def main(argv: Optional[list] = None) -> int:
     parser = argparse.ArgumentParser(
         prog="traffic_classifier_sdn_amd",
@@ -102,6 +132,10 @@ def main(argv: Optional[list] = None) -> int:
                         help="append a Confidence column (top class probability) to the table")
     parser.add_argument("--min-confidence", type=float, default=0.0, metavar="P",
                         help="show flows whose confidence is below P as 'unknown' (implies --confidence)")
+    parser.add_argument("--members", default=DEFAULT_MEMBERS, metavar="A,B,...",
+                        help="ensemble: the subcommand names of the member models")
+    parser.add_argument("--weights", default=None, metavar="W,W,...",
+                        help="ensemble: one positive weight per member (default: equal)")
     args = parser.parse_args(argv)
 
     if args.subcommand == "train":
@@ -133,11 +167,16 @@ def main(argv: Optional[list] = None) -> int:
     from .models import load_model
     from .serve import RealtimeClassifier
 
-    path = _checkpoint_path(args.subcommand, args.models_dir)
-    if not os.path.exists(path):
-        print(f"ERROR: checkpoint {path} not found", file=sys.stderr)
-        return 2
-    model = load_model(path, device=args.device)
+    if args.subcommand == "ensemble":
+        model = _load_ensemble(args)
+        if model is None:
+            return 2
+    else:
+        path = _checkpoint_path(args.subcommand, args.models_dir)
+        if not os.path.exists(path):
+            print(f"ERROR: checkpoint {path} not found", file=sys.stderr)
+            return 2
+        model = load_model(path, device=args.device)
     confidence = args.confidence or args.min_confidence > 0.0
     if confidence and not hasattr(model, "predict_proba"):
         print(f"ERROR: {args.subcommand} has no class probabilities: no --confidence",

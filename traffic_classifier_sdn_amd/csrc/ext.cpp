@@ -7,6 +7,8 @@
 
 #include <ATen/cuda/CUDAContext.h>
 
+#include "ensemble.h"
+
 namespace {
 
 #define CHECK_IN(t, type)                                         \
@@ -32,6 +34,14 @@ void launch_rf_predict(const float*, const unsigned*, const unsigned*,
                        int, int, hipStream_t);
 int launch_rf_scores(const float*, const unsigned*, const int*, const float*,
                      float*, int*, float*, long long, int, int, hipStream_t);
+int launch_gnb_proba(const float*, const double*, const double*,
+                     const double*, float*, long long, int, hipStream_t);
+int launch_linear_proba(const float*, const float*, const float*, float*,
+                        long long, int, hipStream_t);
+int launch_knn_vote_proba(const int*, const unsigned char*, float*, long long,
+                          int, long long, int, hipStream_t);
+int launch_ensemble_vote(const EnsembleArgs*, float*, int*, float*, long long,
+                         int, hipStream_t);
 void launch_svc_predict(const float*, const float*, const float*,
                         const unsigned char*, const float*, int*, long long,
                         int, int, float, hipStream_t);
@@ -192,6 +202,111 @@ static std::vector<torch::Tensor> rf_predict_scores(
       conf.data_ptr<float>(), n, T, (int)C, cur_stream());
   TORCH_CHECK(rc == 0, "rf_predict_scores: no kernel for ", C, " classes");
   return {proba, labels, conf};
+}
+
+// Class probabilities and the soft vote (ensemble_kernels.hip).  Class counts
+// are 2..8; anything else is an error here, never an unwritten output.
+static torch::Tensor gnb_proba(torch::Tensor X, torch::Tensor theta,
+                               torch::Tensor inv_var, torch::Tensor cconst) {
+  CHECK_IN(X, torch::kFloat32);
+  CHECK_IN(theta, torch::kFloat64);
+  CHECK_IN(inv_var, torch::kFloat64);
+  CHECK_IN(cconst, torch::kFloat64);
+  TORCH_CHECK(X.dim() == 2 && X.size(1) == 12, "X must be (n,12)");
+  const int64_t C = cconst.numel();
+  TORCH_CHECK(C >= 2 && C <= 8, "gnb_proba supports 2..8 classes, got ", C);
+  TORCH_CHECK(theta.numel() == C * 12 && inv_var.numel() == C * 12,
+              "theta and inv_var must be (C,12)");
+  const long long n = X.size(0);
+  auto proba = torch::empty({n, C}, X.options());
+  const int rc = launch_gnb_proba(
+      X.data_ptr<float>(), theta.data_ptr<double>(), inv_var.data_ptr<double>(),
+      cconst.data_ptr<double>(), proba.data_ptr<float>(), n, (int)C,
+      cur_stream());
+  TORCH_CHECK(rc == 0, "gnb_proba: no kernel for ", C, " classes");
+  return proba;
+}
+
+static torch::Tensor linear_proba(torch::Tensor X, torch::Tensor W,
+                                  torch::Tensor b) {
+  CHECK_IN(X, torch::kFloat32);
+  CHECK_IN(W, torch::kFloat32);
+  CHECK_IN(b, torch::kFloat32);
+  TORCH_CHECK(X.dim() == 2 && X.size(1) == 12, "X must be (n,12)");
+  const int64_t C = b.numel();
+  TORCH_CHECK(C >= 2 && C <= 8, "linear_proba supports 2..8 classes, got ", C);
+  TORCH_CHECK(W.numel() == C * 12, "W must be (C,12)");
+  const long long n = X.size(0);
+  auto proba = torch::empty({n, C}, X.options());
+  const int rc = launch_linear_proba(X.data_ptr<float>(), W.data_ptr<float>(),
+                                     b.data_ptr<float>(),
+                                     proba.data_ptr<float>(), n, (int)C,
+                                     cur_stream());
+  TORCH_CHECK(rc == 0, "linear_proba: no kernel for ", C, " classes");
+  return proba;
+}
+
+static torch::Tensor knn_vote_proba(torch::Tensor idx, torch::Tensor y,
+                                    int64_t C) {
+  CHECK_IN(idx, torch::kInt32);
+  CHECK_IN(y, torch::kUInt8);
+  TORCH_CHECK(idx.dim() == 2 && idx.size(1) >= 1, "idx must be (n,k), k >= 1");
+  TORCH_CHECK(C >= 2 && C <= 8, "knn_vote_proba supports 2..8 classes, got ", C);
+  const long long n = idx.size(0);
+  auto proba = torch::empty({n, C}, idx.options().dtype(torch::kFloat32));
+  const int rc = launch_knn_vote_proba(
+      idx.data_ptr<int>(), y.data_ptr<unsigned char>(), proba.data_ptr<float>(),
+      n, (int)idx.size(1), (long long)y.numel(), (int)C, cur_stream());
+  TORCH_CHECK(rc == 0, "knn_vote_proba: no kernel for ", C, " classes");
+  return proba;
+}
+
+// Returns (avg [n,C] f32 or an empty tensor, labels [n] i32, conf [n] f32).
+// `weights` are the normalised weights (the caller divides by their f64 sum).
+static std::vector<torch::Tensor> ensemble_vote(
+    std::vector<torch::Tensor> probas,
+    std::vector<std::vector<int64_t>> colmaps, std::vector<double> weights,
+    int64_t C, bool want_proba) {
+  const int64_t M = (int64_t)probas.size();
+  TORCH_CHECK(M >= 1 && M <= ENS_MAX_M, "ensemble_vote takes 1..8 members, got ", M);
+  TORCH_CHECK((int64_t)colmaps.size() == M && (int64_t)weights.size() == M,
+              "ensemble_vote: one column map and one weight per member");
+  TORCH_CHECK(C >= 2 && C <= ENS_MAX_C, "ensemble_vote supports 2..8 classes, got ", C);
+  EnsembleArgs args;
+  memset(&args, 0, sizeof(args));
+  args.M = (int)M;
+  const long long n = probas[0].size(0);
+  for (int64_t m = 0; m < M; ++m) {
+    const torch::Tensor& p = probas[m];
+    CHECK_IN(p, torch::kFloat32);
+    TORCH_CHECK(p.dim() == 2, "member probabilities must be (n,C_m)");
+    TORCH_CHECK(p.size(0) == n, "members differ in their row count");
+    const int64_t cm = p.size(1);
+    TORCH_CHECK(cm >= 2 && cm <= ENS_MAX_C, "a member has ", cm, " classes, not 2..8");
+    TORCH_CHECK((int64_t)colmaps[m].size() == cm,
+                "a column map must have one entry per member class");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(p.data_ptr<float>()) % 16 == 0,
+                "member probabilities must be 16-byte aligned");
+    for (int64_t j = 0; j < cm; ++j) {
+      TORCH_CHECK(colmaps[m][j] >= 0 && colmaps[m][j] < C,
+                  "column map entry ", colmaps[m][j], " outside the ", C, " classes");
+      args.map[m * ENS_MAX_C + j] = (unsigned char)colmaps[m][j];
+    }
+    const float w = (float)weights[m];
+    TORCH_CHECK(std::isfinite(w) && w > 0.f, "weights must be finite and positive");
+    args.p[m] = p.data_ptr<float>();
+    args.w[m] = w;
+    args.cm[m] = (unsigned char)cm;
+  }
+  auto opts = probas[0].options();
+  auto avg = torch::empty({want_proba ? n : 0, C}, opts);
+  auto labels = torch::empty({n}, opts.dtype(torch::kInt32));
+  auto conf = torch::empty({n}, opts);
+  const int rc = launch_ensemble_vote(
+      &args, want_proba ? avg.data_ptr<float>() : nullptr,
+      labels.data_ptr<int>(), conf.data_ptr<float>(), n, (int)C, cur_stream());
+  TORCH_CHECK(rc == 0, "ensemble_vote: arguments out of the kernel's range");
+  return {avg, labels, conf};
 }
 
 static torch::Tensor svc_predict(torch::Tensor X, torch::Tensor SV,
@@ -555,6 +670,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rf_predict", &rf_predict, "packed-forest traversal + vote");
   m.def("rf_predict_scores", &rf_predict_scores,
         "packed-forest traversal, all trees: (proba | empty, labels, conf)");
+  m.def("gnb_proba", &gnb_proba, "GaussianNB class probabilities (f64 softmax)");
+  m.def("linear_proba", &linear_proba, "logistic class probabilities (f64 softmax)");
+  m.def("knn_vote_proba", &knn_vote_proba, "neighbour vote fractions from top-k indices");
+  m.def("ensemble_vote", &ensemble_vote,
+        "soft vote over member probabilities: (avg | empty, labels, conf)");
   m.def("svc_predict", &svc_predict, "RBF Gram + OVO vote");
   m.def("knn_topk", &knn_topk, "brute-force top-k (+fused vote)");
   m.def("knn_topk_mfma", &knn_topk_mfma, "MFMA distance-GEMM top-k (+fused vote)",

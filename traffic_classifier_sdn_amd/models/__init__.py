@@ -3,6 +3,7 @@
 from typing import Any, Dict, Optional
 
 from .base import Estimator
+from .ensemble import SoftVoteEnsemble
 from .gaussian_nb import GaussianNB
 from .kmeans import KMeans
 from .kneighbors import KNeighborsClassifier
@@ -60,6 +61,7 @@ __all__ = [
     "LogisticRegression",
     "RandomForestClassifier",
     "SVC",
+    "SoftVoteEnsemble",
     "from_params",
     "load_model",
     "ALGO_TO_CHECKPOINT",

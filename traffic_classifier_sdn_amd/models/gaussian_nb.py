@@ -83,6 +83,13 @@ class GaussianNB(Estimator):
         ll = ops.gnb_joint_loglik(Xt, self.theta_, self.var_, self.class_prior_)
         return torch.softmax(ll, dim=1).cpu().numpy()
 
+    def predict_proba_device(self, X: ArrayLike) -> torch.Tensor:
+        """predict_proba as an f32 [n,C] tensor on the model's device: one
+        kernel on the GPU, no host round trip (the soft-vote ensemble's
+        input)."""
+        Xt = as_tensor(X, self.device, torch.float32)
+        return ops.gnb_proba(Xt, self.theta_, self.var_, self.class_prior_)
+
     # -- checkpointing -------------------------------------------------
     def to_params(self) -> Dict[str, Any]:
         return {

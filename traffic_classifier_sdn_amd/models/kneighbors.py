@@ -117,6 +117,19 @@ class KNeighborsClassifier(Estimator):
         # smaller than n_neighbors
         return (counts / lab.shape[1]).cpu().numpy()
 
+    def predict_proba_device(self, X: ArrayLike) -> torch.Tensor:
+        """predict_proba as an f32 [n,C] tensor on the model's device:
+        kneighbors, then the vote-fraction kernel, which skips the -1
+        padding of a reference set smaller than n_neighbors.  Not for a
+        sharded reference set."""
+        if self.sharded_:
+            raise NotImplementedError(
+                "predict_proba_device does not merge the shards of a sharded KNeighborsClassifier"
+            )
+        Xt = as_tensor(X, self.device, torch.float32)
+        _, idx_k = self.kneighbors(Xt)
+        return ops.knn_vote_proba(idx_k, self.y_, len(self.classes_))
+
     # -- checkpointing -------------------------------------------------
     def to_params(self) -> Dict[str, Any]:
         return {

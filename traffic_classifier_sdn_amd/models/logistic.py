@@ -93,6 +93,13 @@ class LogisticRegression(Estimator):
         logits = self.decision_function(X)
         return torch.softmax(logits.double(), dim=1).cpu().numpy()
 
+    def predict_proba_device(self, X: ArrayLike) -> torch.Tensor:
+        """predict_proba as an f32 [n,C] tensor on the model's device: one
+        kernel on the GPU, no host round trip (the soft-vote ensemble's
+        input)."""
+        Xt = as_tensor(X, self.device, torch.float32)
+        return ops.linear_proba(Xt, self.coef_, self.intercept_)
+
     # -- checkpointing -------------------------------------------------
     def to_params(self) -> Dict[str, Any]:
         coef = getattr(self, "_coef64", self.coef_.double()).cpu().numpy()

@@ -224,6 +224,15 @@ class RandomForestClassifier(Estimator):
         Xt = as_tensor(X, self.device, torch.float32)
         return ops.rf_predict_proba(Xt, self.forest)
 
+    predict_proba_device = predict_proba  # already an f32 device tensor
+
+    def predict_scores(self, X: ArrayLike):
+        """(proba f32[n,C], idx int32[n], conf float32[n]) device tensors
+        from ONE pass over all trees: predict_proba and predict_index_conf
+        together."""
+        Xt = as_tensor(X, self.device, torch.float32)
+        return ops.rf_predict_scores(Xt, self.forest, want_proba=True)
+
     def predict_log_proba(self, X: ArrayLike) -> torch.Tensor:
         """log of predict_proba; -inf where no tree votes for a class
         (sklearn API)."""

@@ -50,7 +50,10 @@ def __getattr__(name):
         raise AttributeError(name)
 
     def dispatcher(*args, **kwargs):
-        first = next((a for a in args if isinstance(a, torch.Tensor)), None)
+        # a list of tensors (ensemble_vote's members) counts through its
+        # first element
+        flat = (a[0] if isinstance(a, (list, tuple)) and a else a for a in args)
+        first = next((a for a in flat if isinstance(a, torch.Tensor)), None)
         mod = _mod_for(first) if first is not None else _cpu
         fn = getattr(mod, name, None)
         if fn is None:

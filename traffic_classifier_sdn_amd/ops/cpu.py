@@ -355,6 +355,118 @@ def rf_predict_scores(
 
 
 # ----------------------------------------------------------------------
+# Class probabilities as f32 tensors, and the soft vote over them (CPU
+# oracles of csrc/ensemble_kernels.hip)
+# ----------------------------------------------------------------------
+
+
+def gnb_proba(
+    X: torch.Tensor, theta: torch.Tensor, var: torch.Tensor, class_prior: torch.Tensor
+) -> torch.Tensor:
+    """softmax of the joint log-likelihoods, computed in f64, as f32 [n,C]."""
+    ll = gnb_joint_loglik(X.double(), theta.double(), var.double(), class_prior.double())
+    return torch.softmax(ll, dim=1).to(torch.float32)
+
+
+def linear_proba(X: torch.Tensor, coef: torch.Tensor, intercept: torch.Tensor) -> torch.Tensor:
+    """softmax of the logits, computed in f64 from the parameters as they
+    are stored, as f32 [n,C]."""
+    logits = linear_logits(X.double(), coef.double(), intercept.double())
+    return torch.softmax(logits, dim=1).to(torch.float32)
+
+
+def knn_vote_proba(idx: torch.Tensor, y: torch.Tensor, n_classes: int) -> torch.Tensor:
+    """Neighbour vote fractions: proba[c] = count[c] / k_valid as an f32
+    division.  An entry with idx < 0 is padding and is not counted; k_valid
+    is the number of counted entries (the contract is k_valid >= 1)."""
+    if not 2 <= int(n_classes) <= 8:
+        raise ValueError(f"knn_vote_proba supports 2..8 classes, got {n_classes}")
+    idx = idx.long()
+    valid = idx >= 0
+    lab = y.long()[idx.clamp(min=0)]
+    classes = torch.arange(n_classes, device=idx.device)
+    hit = (lab.unsqueeze(2) == classes) & valid.unsqueeze(2)  # (n, k, C)
+    count = hit.sum(dim=1).to(torch.float32)
+    return count / valid.sum(dim=1, keepdim=True).to(torch.float32)
+
+
+def ensemble_weights(weights, n_members: int):
+    """Member weights as the vote uses them: divided by their f64 sum, then
+    rounded to f32 (returned as Python floats).  ``None`` means equal
+    weights.  ValueError for a wrong count, and for a weight that is not
+    finite, not positive, or whose total is zero."""
+    if weights is None:
+        weights = [1.0] * n_members
+    w = np.asarray([float(v) for v in weights], dtype=np.float64)
+    if w.shape != (n_members,):
+        raise ValueError(f"{w.size} weights for {n_members} ensemble members")
+    if not bool(np.isfinite(w).all()) or bool((w <= 0.0).any()):
+        raise ValueError("ensemble weights must be finite and positive")
+    total = float(w.sum())
+    if not np.isfinite(total) or total <= 0.0:
+        raise ValueError("ensemble weights must have a finite, positive total")
+    w32 = (w / total).astype(np.float32)
+    if bool((w32 <= 0.0).any()):
+        raise ValueError("an ensemble weight vanishes next to the others")
+    return [float(v) for v in w32]
+
+
+def ensemble_check(probas, colmaps, weights, n_classes: int):
+    """Argument rules of ensemble_vote, shared by the CPU and GPU bindings:
+    1..8 members of 2..8 classes with one row count, one map entry below
+    ``n_classes`` per member column, ``n_classes`` in 2..8.  Returns the
+    normalised f32 weights."""
+    M = len(probas)
+    if not 1 <= M <= 8:
+        raise ValueError(f"ensemble_vote takes 1..8 members, got {M}")
+    if not 2 <= int(n_classes) <= 8:
+        raise ValueError(f"ensemble_vote supports 2..8 classes, got {n_classes}")
+    if len(colmaps) != M:
+        raise ValueError(f"{len(colmaps)} column maps for {M} ensemble members")
+    n = probas[0].shape[0]
+    for p, cmap in zip(probas, colmaps):
+        if p.dim() != 2 or not 2 <= p.shape[1] <= 8:
+            raise ValueError(f"member probabilities must be (n, 2..8), got {tuple(p.shape)}")
+        if p.shape[0] != n:
+            raise ValueError(f"members differ in their row count: {p.shape[0]} and {n}")
+        if len(cmap) != p.shape[1]:
+            raise ValueError(f"{len(cmap)} map entries for {p.shape[1]} member classes")
+        if any(not 0 <= int(c) < n_classes for c in cmap):
+            raise ValueError(f"column map {list(cmap)} points outside {n_classes} classes")
+    return ensemble_weights(weights, M)
+
+
+def ensemble_vote(
+    probas, colmaps, weights, n_classes: int, want_proba: bool = True
+) -> Tuple[Optional[torch.Tensor], torch.Tensor, torch.Tensor]:
+    """Soft vote: (avg[n,C] f32 | None, label[n] int32, conf[n] f32).
+
+    ``probas[m]`` is member m's [n, C_m] f32 probabilities, ``colmaps[m][j]``
+    the ensemble column of its column j and ``weights[m]`` its weight
+    (normalised here, see ensemble_weights).  Per row avg starts at zero and
+    takes, in member order, avg[col] = fma(w_m, p_m[j], avg[col]) in f32; a
+    class a member lacks gets nothing from it.  label is the first-maximum
+    argmax of avg and conf its maximum.
+
+    The fused step is formed in f64, where the product of two f32 values is
+    exact, and rounded to f32: the kernel's fmaf up to the double rounding
+    of the sum.
+    """
+    w32 = ensemble_check(probas, colmaps, weights, n_classes)
+    n = probas[0].shape[0]
+    avg = torch.zeros(n, n_classes, dtype=torch.float32, device=probas[0].device)
+    for p, cmap, w in zip(probas, colmaps, w32):
+        p64 = p.to(torch.float32).double()
+        for j, col in enumerate(cmap):
+            avg[:, col] = (avg[:, col].double() + w * p64[:, j]).to(torch.float32)
+    conf, label = avg.max(dim=1)
+    # torch.max returns the first maximum on CPU and leaves the choice open
+    # on other devices: take the first column that reaches it
+    label = torch.argmax((avg == conf.unsqueeze(1)).to(torch.uint8), dim=1)
+    return (avg if want_proba else None), label.to(torch.int32), conf
+
+
+# ----------------------------------------------------------------------
 # Serve-path feature extraction (CPU oracle of the GPU kernel; mirrors the
 # reference Flow update math, traffic_classifier.py:63-96)
 # ----------------------------------------------------------------------

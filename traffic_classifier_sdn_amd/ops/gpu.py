@@ -359,6 +359,71 @@ def rf_predict_proba(X: torch.Tensor, forest: Dict[str, torch.Tensor]) -> torch.
 
 
 # ----------------------------------------------------------------------
+# class probabilities and the soft vote (csrc/ensemble_kernels.hip)
+# ----------------------------------------------------------------------
+
+ensemble_weights = _cpu.ensemble_weights
+ensemble_check = _cpu.ensemble_check
+
+# entry = (theta_ref, var_ref, prior_ref, theta64, inv_var64, const64); the
+# first three pin the source buffers, as in _gnb_cache
+_gnb_proba_cache: Dict[Tuple[int, int, int], Tuple[torch.Tensor, ...]] = {}
+
+
+def gnb_proba(
+    X: torch.Tensor, theta: torch.Tensor, var: torch.Tensor, class_prior: torch.Tensor
+) -> torch.Tensor:
+    if X.shape[1] != 12:
+        return _cpu.gnb_proba(X, theta, var, class_prior)
+    key = (theta.data_ptr(), var.data_ptr(), class_prior.data_ptr())
+    ent = _gnb_proba_cache.get(key)
+    if ent is None:
+        if len(_gnb_proba_cache) > 32:
+            _gnb_proba_cache.clear()
+        var64 = var.double()
+        const = torch.log(class_prior.double()) - 0.5 * torch.log(2.0 * torch.pi * var64).sum(dim=1)
+        ent = (theta, var, class_prior, _f64(theta), (1.0 / var64).contiguous(), const.contiguous())
+        _gnb_proba_cache[key] = ent
+    return _ext.gnb_proba(_f32(X), ent[3], ent[4], ent[5])
+
+
+def linear_proba(X: torch.Tensor, coef: torch.Tensor, intercept: torch.Tensor) -> torch.Tensor:
+    if X.shape[1] != 12:
+        return _cpu.linear_proba(X, coef, intercept)
+    return _ext.linear_proba(_f32(X), _f32_cached(coef), _f32_cached(intercept))
+
+
+# entry = (y_ref, y8): y_ref pins the label buffer
+_knn_y8_cache: Dict[Tuple[int, int, torch.dtype], Tuple[torch.Tensor, torch.Tensor]] = {}
+
+
+def knn_vote_proba(idx: torch.Tensor, y: torch.Tensor, n_classes: int) -> torch.Tensor:
+    if y.dtype == torch.uint8 and y.is_contiguous():
+        y8 = y
+    else:
+        key = (y.data_ptr(), y.numel(), y.dtype)
+        ent = _knn_y8_cache.get(key)
+        if ent is None:
+            if len(_knn_y8_cache) > 16:
+                _knn_y8_cache.clear()
+            ent = (y, y.to(torch.uint8).contiguous())
+            _knn_y8_cache[key] = ent
+        y8 = ent[1]
+    return _ext.knn_vote_proba(idx.to(torch.int32).contiguous(), y8, int(n_classes))
+
+
+def ensemble_vote(
+    probas, colmaps, weights, n_classes: int, want_proba: bool = True
+) -> Tuple[Optional[torch.Tensor], torch.Tensor, torch.Tensor]:
+    w32 = _cpu.ensemble_check(probas, colmaps, weights, n_classes)
+    avg, labels, conf = _ext.ensemble_vote(
+        [_f32(p) for p in probas], [[int(c) for c in m] for m in colmaps], w32,
+        int(n_classes), bool(want_proba),
+    )
+    return (avg if want_proba else None), labels, conf
+
+
+# ----------------------------------------------------------------------
 # fit ops
 # ----------------------------------------------------------------------
 

@@ -9,12 +9,18 @@ launches, sized for a 1 ms poll cadence.
 
 Buffers are fixed-capacity (graphs need static shapes); flows beyond
 capacity fall back to a plain (non-graph) launch path.
+
+``ensemble=[names]`` adds a soft vote over those models' class probabilities
+(models/ensemble.py): the result gains the key ``"ensemble"`` (indices into
+``engine.ensemble.classes_``) and ``engine.confidence`` its averaged top
+probability.  The members' probability kernels and the vote kernel are part
+of the same captured graph.
 """
 
 from __future__ import annotations
 
 import time
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -31,6 +37,8 @@ class GpuServeEngine:
         use_graph: bool = True,
         device: str = "cuda",
         confidence: bool = False,
+        ensemble: Optional[Sequence[str]] = None,
+        ensemble_weights: Optional[Sequence[float]] = None,
     ) -> None:
         self.models = models
         self.capacity = capacity
@@ -54,6 +62,32 @@ class GpuServeEngine:
         )
         self.d_conf: Dict[str, torch.Tensor] = {}
         self.h_conf: Dict[str, torch.Tensor] = {}
+        # soft vote over the named models; None leaves the pass as it is
+        self.ensemble = None
+        self._ens_members: List[str] = []
+        if ensemble:
+            from .models.ensemble import SoftVoteEnsemble
+            from .models.kneighbors import KNeighborsClassifier
+
+            names = list(ensemble)
+            if "ensemble" in models:
+                raise ValueError("with ensemble=, no model can be named 'ensemble'")
+            if len(set(names)) != len(names):
+                raise ValueError(f"ensemble names a model twice: {names}")
+            missing = [n for n in names if n not in models]
+            if missing:
+                raise ValueError(f"ensemble members {missing} are not in models")
+            if self.use_graph:
+                knn = [n for n in names if isinstance(models[n], KNeighborsClassifier)]
+                if knn:
+                    raise ValueError(
+                        f"ensemble member {knn[0]!r} is a KNN model, which this engine "
+                        "does not capture: use use_graph=False"
+                    )
+            self.ensemble = SoftVoteEnsemble({n: models[n] for n in names}, ensemble_weights)
+            self._ens_members = names
+        # every key of self.confidence, in order
+        self._conf_keys = self._conf_models + (["ensemble"] if self.ensemble else [])
         self.confidence: Dict[str, np.ndarray] = {}
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self.last_latency_s = 0.0
@@ -63,24 +97,47 @@ class GpuServeEngine:
         from . import ops
 
         X = ops.flow_features(self.d_cur, self.d_prev, self.d_times)
-        pin = self.device.type == "cuda"
+        for name, labels, conf in self._predict_all(X):
+            if conf is not None:
+                self._keep(self.d_conf, self.h_conf, name, conf)
+            self._keep(self.d_labels, self.h_labels, name, labels)
+
+    def _keep(self, dev: Dict[str, torch.Tensor], host: Dict[str, torch.Tensor],
+              name: str, value: torch.Tensor) -> None:
+        """Into the static buffer of that name (the first call makes it)."""
+        if name in dev:
+            dev[name].copy_(value)
+        else:
+            dev[name] = value
+            host[name] = torch.empty_like(
+                value, device="cpu", pin_memory=self.device.type == "cuda"
+            )
+
+    def _predict_all(self, X: torch.Tensor):
+        """Yields (name, labels, conf | None) per model, then the vote's.
+        A member's probabilities come from its own kernel next to its
+        unchanged label kernel, except the forest's: a forest is walked once
+        per poll, by the scores kernel, which gives its probabilities, and
+        its labels and confidence where it is a confidence model too."""
+        probas: Dict[str, torch.Tensor] = {}
         for name, model in self.models.items():
-            if name in self._conf_models:
-                labels, conf = model.predict_index_conf(X)
-                if name in self.d_conf:
-                    self.d_conf[name].copy_(conf)
+            member = name in self._ens_members
+            conf = None
+            if member and hasattr(model, "predict_scores"):
+                probas[name], labels, c = model.predict_scores(X)
+                if name in self._conf_models:
+                    conf = c
+            else:
+                if name in self._conf_models:
+                    labels, conf = model.predict_index_conf(X)
                 else:
-                    self.d_conf[name] = conf
-                    self.h_conf[name] = torch.empty_like(conf, device="cpu", pin_memory=pin)
-            else:
-                labels = model.predict_index(X)
-            if name in self.d_labels:
-                self.d_labels[name].copy_(labels)
-            else:
-                self.d_labels[name] = labels
-                self.h_labels[name] = torch.empty_like(
-                    labels, device="cpu", pin_memory=pin
-                )
+                    labels = model.predict_index(X)
+                if member:
+                    probas[name] = model.predict_proba_device(X)
+            yield name, labels, conf
+        if self.ensemble is not None:
+            _, labels, conf = self.ensemble.vote([probas[n] for n in self._ens_members])
+            yield "ensemble", labels, conf
 
     def _capture(self) -> None:
         s = torch.cuda.Stream()
@@ -100,7 +157,8 @@ class GpuServeEngine:
         """Run one classification pass over every live flow; returns
         {model_name: labels[n] int32} (class indices).  With
         ``confidence=True`` the pass also leaves {model_name: float32[n]} in
-        ``self.confidence`` for the models that support it."""
+        ``self.confidence`` for the models that support it.  With
+        ``ensemble=`` both carry the vote's under the key "ensemble"."""
         n = len(table)
         t0 = time.perf_counter()
         if n > self.capacity:
@@ -120,24 +178,25 @@ class GpuServeEngine:
             else:
                 self._compute()
             out = {}
-            for name in self.models:
+            keys = list(self.models) + (["ensemble"] if self.ensemble else [])
+            for name in keys:
                 self.h_labels[name].copy_(self.d_labels[name], non_blocking=True)
-            for name in self._conf_models:
+            for name in self._conf_keys:
                 self.h_conf[name].copy_(self.d_conf[name], non_blocking=True)
             torch.cuda.synchronize()
-            for name in self.models:
+            for name in keys:
                 out[name] = self.h_labels[name][:n].numpy().copy()
             self.confidence = {
-                name: self.h_conf[name][:n].numpy().copy() for name in self._conf_models
+                name: self.h_conf[name][:n].numpy().copy() for name in self._conf_keys
             }
         else:
             self.d_cur.copy_(self.h_cur)
             self.d_prev.copy_(self.h_prev)
             self.d_times.copy_(self.h_times)
             self._compute()
-            out = {name: self.d_labels[name][:n].numpy().copy() for name in self.models}
+            out = {name: self.d_labels[name][:n].numpy().copy() for name in self.d_labels}
             self.confidence = {
-                name: self.d_conf[name][:n].numpy().copy() for name in self._conf_models
+                name: self.d_conf[name][:n].numpy().copy() for name in self._conf_keys
             }
         self.last_latency_s = time.perf_counter() - t0
         return out
@@ -151,12 +210,9 @@ class GpuServeEngine:
         X = ops.flow_features(to(cur), to(prev), to(times))
         out = {}
         self.confidence = {}
-        for name, model in self.models.items():
-            if name in self._conf_models:
-                labels, conf = model.predict_index_conf(X)
+        for name, labels, conf in self._predict_all(X):
+            if conf is not None:
                 self.confidence[name] = conf.cpu().numpy()
-            else:
-                labels = model.predict_index(X)
             out[name] = labels.cpu().numpy()
         self.last_latency_s = time.perf_counter() - t0
         return out
