@@ -220,11 +220,16 @@ __global__ void rf_predict_kernel(const float* __restrict__ X,
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint2* s_nodes = reinterpret_cast<uint2*>(smem);
   float* s_probs = reinterpret_cast<float*>(s_nodes + (LDS_NODES ? n_nodes : 0));
-  // LDS_FEAT: each thread's 12 features live in LDS at pitch 13 (gcd(13,32)
-  // = 1 -> the 32 lanes of a group land on distinct banks) and the per-node
-  // runtime feature pick is ONE ds_read_b32 instead of sel12's ~10-op
-  // register select tree — trading idle LDS-pipe cycles for the VALU issue
-  // slots this kernel is bound on (VALUBusy 99.2%).
+  // LDS_FEAT: each thread's 12 features live in LDS at pitch 13 and the
+  // per-node runtime feature pick is ONE ds_read_b32 instead of sel12's
+  // ~10-op register select tree — trading idle LDS-pipe cycles for the VALU
+  // issue slots this kernel is bound on (VALUBusy 99.2%).  Pitch 13
+  // (gcd(13,32) = 1) puts the 32 lanes of a group on distinct banks only
+  // while they read the same feature; lanes at different depths of a tree
+  // do not, so the read does pay bank conflicts.  The feature-major rows of
+  // the streaming kernel below avoid them; here, with the node table in
+  // L2, they measured level (profiles/rf_predict_stream2.md) and the layout
+  // stayed.
   float* s_feat = s_probs + (LDS_PROBS ? n_leaves * C : 0);
 
   if (LDS_NODES)
@@ -299,8 +304,8 @@ __global__ void rf_predict_kernel(const float* __restrict__ X,
   }
 }
 
-// Streaming variant (mode 4, the large-batch default): a LANE, not a wave,
-// is the unit that advances through trees and rows.  The row-per-lane
+// Streaming variant (modes 4, 5 and 6; the large-batch default): a LANE, not
+// a wave, is the unit that advances through trees and rows.  The row-per-lane
 // kernel above reconverges after every tree and leaves together, so a wave
 // pays the deepest path of its 64 lanes in every tree and the slowest row's
 // exit: 765 node visits per row where the row itself needs 322
@@ -311,7 +316,13 @@ __global__ void rf_predict_kernel(const float* __restrict__ X,
 //  * It walks rf_pack's STREAM table (layout there).  A leaf's link is the
 //    next tree's root, so a lane steps from leaf to root with no roots[]
 //    load; a leaf "goes right" because its byte is clamped to slot 12 of the
-//    lane's pitch-13 LDS row, which holds NaN.
+//    lane's 13-slot LDS row, which holds NaN.
+//  * The LDS rows are FEATURE-MAJOR: slot j of thread tid is
+//    s_feat[j * blockDim.x + tid].  Every lane is at a node of its own and
+//    asks for a feature of its own, and in this layout the bank is
+//    tid mod 32 whatever j is, so the read (and the 12 stores of a refill)
+//    never conflict.  One row per thread at pitch 13, the earlier layout,
+//    is conflict-free only when all lanes read the same slot.
 //  * The leaf byte carries the vote shift, so the pure-leaf count is one
 //    shift and one add; mixed leaves (rare) read their row under a branch.
 //  * The majority test belongs to whole trees (t & 7 == 7, once it can
@@ -336,7 +347,20 @@ __global__ void rf_predict_kernel(const float* __restrict__ X,
 // order, mixed leaves added to acc in that order, the majority test after
 // the same trees, first-maximum argmax — labels do not depend on which lane
 // ran a row or when.
-template <int C, bool LDS_NODES>
+//
+// R rows per lane (mode 6: R = 2, LDS node table only).  One block per CU
+// is all the LDS admits and a block is at most 16 waves, so further
+// independent chains have to come from inside the lane: a lane carries R
+// SLOTS, each with the full per-row state above and a feature row of its own
+// (slot s, feature j at s_feat[(s * 13 + j) * blockDim.x + tid]).  An
+// iteration issues the R node reads, then the R feature reads, then does
+// the R updates, so the two LDS latencies of a visit overlap across slots
+// and the loop's scalar work (branches, ballot, budget) is shared by R
+// visits.  A pass serves slot 0 and then slot 1, the cursor running on from
+// one to the other; `waiting`, `pass_min` and the exit condition count
+// slots, R x 64 per wave.  In every iteration some slot advances, so the
+// iteration bound is unchanged.
+template <int C, bool LDS_NODES, int R>
 __launch_bounds__(LDS_NODES ? 1024 : 256)
 __global__ void rf_predict_stream_kernel(const float* __restrict__ X,
                                          const uint2* __restrict__ snodes,
@@ -344,11 +368,16 @@ __global__ void rf_predict_stream_kernel(const float* __restrict__ X,
                                          int* __restrict__ out, long long n,
                                          int rows_per_wave, int n_nodes,
                                          int n_leaves, int T, int pass_min) {
+  static_assert(R == 1 || (R == 2 && LDS_NODES), "two rows per lane need the LDS table");
+  constexpr int BLOCK = LDS_NODES ? 1024 : 256;  // the launcher's block size
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint2* s_nodes = reinterpret_cast<uint2*>(smem);
+  // slot j of this thread's row s: my_feat[(s * 13 + j) * BLOCK]
   float* my_feat = reinterpret_cast<float*>(s_nodes + (LDS_NODES ? n_nodes + 2 : 0)) +
-                   (int)threadIdx.x * 13;
-  my_feat[12] = __uint_as_float(0x7fc00000u);  // NaN: leaves compare false
+                   (int)threadIdx.x;
+#pragma unroll
+  for (int s = 0; s < R; ++s)  // NaN: leaves compare false
+    my_feat[(s * 13 + 12) * BLOCK] = __uint_as_float(0x7fc00000u);
   if (LDS_NODES) {
     for (int i = threadIdx.x; i < n_nodes + 2; i += blockDim.x) s_nodes[i] = snodes[i];
     __syncthreads();
@@ -356,10 +385,15 @@ __global__ void rf_predict_stream_kernel(const float* __restrict__ X,
 
   const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const long long begin =
-      ((long long)blockIdx.x * (blockDim.x >> 6) + wave_in_block) * rows_per_wave;
-  if (begin >= n) return;  // wave-uniform
+      ((long long)blockIdx.x * (BLOCK >> 6) + wave_in_block) * rows_per_wave;
   const long long left = n - begin;
-  const int count = left < (long long)rows_per_wave ? (int)left : rows_per_wave;
+  // The range is the same for all lanes; readfirstlane says so to the
+  // compiler, which otherwise does the 64-bit product above in vector
+  // registers and with it everything that follows from `count`: cursor,
+  // budget, waiting and trigger, and every branch of the loop on them.
+  const int count = __builtin_amdgcn_readfirstlane(
+      left < (long long)rows_per_wave ? (int)(left > 0 ? left : 0) : rows_per_wave);
+  if (count <= 0) return;  // wave-uniform
   const float* __restrict__ Xw = X + begin * 12;
   int* __restrict__ outw = out + begin;
   const unsigned park = (unsigned)n_nodes + 1u;
@@ -368,84 +402,110 @@ __global__ void rf_predict_stream_kernel(const float* __restrict__ X,
   int cursor = 0;  // next unassigned row of the range
   int waiting = 0, trigger = 0;
   long long budget = (long long)count * (n_nodes + 2);
-  // per lane; every lane starts idle: parked with nothing to resume
-  unsigned idx = park, resume = park;
-  int row = 0, t = 0;
-  float acc[C];
+  // per slot; every slot starts idle: parked with nothing to resume
+  unsigned idx[R], resume[R];
+  int row[R], t[R];
+  float acc[R][C];
+  unsigned long long votes[R];  // 10-bit packed per-class pure counts
 #pragma unroll
-  for (int c = 0; c < C; ++c) acc[c] = 0.f;
-  unsigned long long votes = 0ull;  // 10-bit packed per-class pure counts
+  for (int s = 0; s < R; ++s) {
+    idx[s] = park;
+    resume[s] = park;
+    row[s] = 0;
+    t[s] = 0;
+    votes[s] = 0ull;
+#pragma unroll
+    for (int c = 0; c < C; ++c) acc[s][c] = 0.f;
+  }
 
   while (true) {
-    if (waiting >= trigger) {  // PASS: serve the parked lanes
-      if (idx == park && resume != park) {  // waits at a flagged leaf
-        float m1 = -INFINITY, m2 = -INFINITY;
-        int bi = 0;
+    if (waiting >= trigger) {  // PASS: serve the parked slots, slot by slot
+      int nidle_all = 0;
 #pragma unroll
-        for (int c = 0; c < C; ++c) {
-          // same values as the row-per-lane kernel's if/else-if, as selects
-          const float sc = acc[c] + vote_count(votes, c);
-          const bool lead = sc > m1;
-          m2 = lead ? m1 : (sc > m2 ? sc : m2);
-          m1 = lead ? sc : m1;
-          bi = lead ? c : bi;
+      for (int s = 0; s < R; ++s) {
+        if (idx[s] == park && resume[s] != park) {  // waits at a flagged leaf
+          float m1 = -INFINITY, m2 = -INFINITY;
+          int bi = 0;
+#pragma unroll
+          for (int c = 0; c < C; ++c) {
+            // same values as the row-per-lane kernel's if/else-if, as selects
+            const float sc = acc[s][c] + vote_count(votes[s], c);
+            const bool lead = sc > m1;
+            m2 = lead ? m1 : (sc > m2 ? sc : m2);
+            m1 = lead ? sc : m1;
+            bi = lead ? c : bi;
+          }
+          // t trees are done, T - t are left; a link to n_nodes ends the row
+          if (resume[s] >= (unsigned)n_nodes || m1 - m2 > (float)(T - t[s])) {
+            outw[row[s]] = bi;
+            resume[s] = park;  // idle
+          } else {
+            idx[s] = resume[s];
+          }
         }
-        // t trees are done, T - t are left; a link to n_nodes ends the row
-        if (resume >= (unsigned)n_nodes || m1 - m2 > (float)(T - t)) {
-          outw[row] = bi;
-          resume = park;  // idle
-        } else {
-          idx = resume;
+        const unsigned long long idle = __ballot(idx[s] == park);
+        int nidle = __popcll(idle);
+        if (cursor < count) {
+          // idle lanes take rows cursor, cursor+1, ... in lane order
+          const int r = cursor + (int)__builtin_amdgcn_mbcnt_hi(
+                                     (unsigned)(idle >> 32),
+                                     __builtin_amdgcn_mbcnt_lo((unsigned)idle, 0u));
+          if (idx[s] == park && r < count) {
+            Row12 x = load_row12(Xw, r);
+#pragma unroll
+            for (int j = 0; j < 12; ++j) my_feat[(s * 13 + j) * BLOCK] = x.v[j];
+#pragma unroll
+            for (int c = 0; c < C; ++c) acc[s][c] = 0.f;
+            votes[s] = 0ull;
+            row[s] = r;
+            t[s] = 0;
+            idx[s] = 0;
+          }
+          const int take = min(nidle, count - cursor);
+          cursor += take;
+          nidle -= take;
         }
+        nidle_all += nidle;
       }
-      const unsigned long long idle = __ballot(idx == park);
-      int nidle = __popcll(idle);
-      if (cursor < count) {
-        // idle lanes take rows cursor, cursor+1, ... in lane order
-        const int r = cursor + (int)__builtin_amdgcn_mbcnt_hi(
-                                   (unsigned)(idle >> 32),
-                                   __builtin_amdgcn_mbcnt_lo((unsigned)idle, 0u));
-        if (idx == park && r < count) {
-          Row12 x = load_row12(Xw, r);
-#pragma unroll
-          for (int j = 0; j < 12; ++j) my_feat[j] = x.v[j];
-#pragma unroll
-          for (int c = 0; c < C; ++c) acc[c] = 0.f;
-          votes = 0ull;
-          row = r;
-          t = 0;
-          idx = 0;
-        }
-        const int take = min(nidle, count - cursor);
-        cursor += take;
-        nidle -= take;
-      }
-      if (nidle == WAVE) break;  // range used up and every lane idle
-      // lanes still idle stay so; the next pass is due when pass_min lanes
+      if (nidle_all == R * WAVE) break;  // range used up and every slot idle
+      // slots still idle stay so; the next pass is due when pass_min slots
       // wait, or all that still run
-      trigger = min(pass_min, WAVE - nidle);
+      trigger = min(pass_min, R * WAVE - nidle_all);
       waiting = 0;
     }
-    if (--budget < 0) break;  // not a table rf_pack made
+    if (budget == 0) break;  // not a table rf_pack made
+    --budget;
 
-    const uint2 node = LDS_NODES ? s_nodes[idx] : snodes[idx];
-    const unsigned byte = node.y & 0xffu;
-    const float fv = my_feat[min(byte, 12u)];
-    unsigned next = (fv <= __uint_as_float(node.x)) ? idx + 1u : node.y >> 8;
-    next = min(next, park);
-    if (byte >= 0x80u) {  // leaf (some lane is at one nearly every step)
-      votes += 1ull << (byte & 63u);
-      ++t;
-      if (node.x != 0u) {  // mixed leaf: row + 1 of its distribution
-        const int pr = (int)min(node.x - 1u, (unsigned)(n_leaves - 1)) * C;
+    // one visit per slot: all node reads, then all feature reads, then the
+    // updates, so the slots' LDS latencies overlap
+    uint2 node[R];
+    unsigned byte[R];
+    float fv[R];
 #pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] += leaf_proba[pr + c];
-      }
+    for (int s = 0; s < R; ++s) node[s] = LDS_NODES ? s_nodes[idx[s]] : snodes[idx[s]];
+#pragma unroll
+    for (int s = 0; s < R; ++s) {
+      byte[s] = node[s].y & 0xffu;
+      fv[s] = my_feat[(s * 13 + (int)min(byte[s], 12u)) * BLOCK];
     }
-    const bool flagged = byte >= 0xc0u;  // leaf of a tree the test follows
-    waiting += __popcll(__ballot(flagged));
-    resume = flagged ? next : resume;
-    idx = flagged ? park : next;
+#pragma unroll
+    for (int s = 0; s < R; ++s) {
+      unsigned next = (fv[s] <= __uint_as_float(node[s].x)) ? idx[s] + 1u : node[s].y >> 8;
+      next = min(next, park);
+      if (byte[s] >= 0x80u) {  // leaf (some lane is at one nearly every step)
+        votes[s] += 1ull << (byte[s] & 63u);
+        ++t[s];
+        if (node[s].x != 0u) {  // mixed leaf: row + 1 of its distribution
+          const int pr = (int)min(node[s].x - 1u, (unsigned)(n_leaves - 1)) * C;
+#pragma unroll
+          for (int c = 0; c < C; ++c) acc[s][c] += leaf_proba[pr + c];
+        }
+      }
+      const bool flagged = byte[s] >= 0xc0u;  // leaf of a tree the test follows
+      waiting += __popcll(__ballot(flagged));
+      resume[s] = flagged ? next : resume[s];
+      idx[s] = flagged ? park : next;
+    }
   }
 }
 
@@ -502,12 +562,19 @@ __launch_bounds__(256) __global__ void rf_predict_wave_kernel(
   }
 }
 
-// Below this many rows the default stays with the row-per-lane kernel: the
-// streaming kernel runs one 1024-thread block per CU, each stages the node
-// table, and a wave wants many rows to refill from.  Measured crossover on
-// the reference forest: behind at 2M rows, level at 4M, +8% at 10M
-// (profiles/rf_predict_stream.md).
-#define RF_STREAM_MIN_ROWS 4000000
+// Below RF_STREAM_MIN_ROWS rows the default stays with the row-per-lane
+// kernel: the streaming kernel runs one 1024-thread block per CU, each
+// stages the node table, and a wave wants many rows to refill from.  With
+// two rows per lane a wave wants twice as many, so mode 6 takes over from
+// mode 5 at RF_STREAM2_MIN_ROWS.  Measured on the reference forest, ms per
+// call for modes 2 / 5 / 6 (profiles/rf_predict_stream2.md): 500k rows
+// 0.225 / 0.234 / 0.232, 750k 0.362 / 0.308 / 0.321, 1.5M 0.601 / 0.515 /
+// 0.513, 2M 0.784 / 0.654 / 0.629, 10M 3.79 / 2.89 / 2.55.
+#define RF_STREAM_MIN_ROWS 750000
+#define RF_STREAM2_MIN_ROWS 1500000
+// Mode 6's parked slots (of 128 per wave) that start a pass: 24 and 32 are
+// level, 16 and 48 behind (same profile).
+#define RF_STREAM_REFILL2 32
 
 extern "C" void launch_rf_predict(const float* X, const unsigned* nodes,
                                   const unsigned* snodes, const int* roots,
@@ -516,9 +583,12 @@ extern "C" void launch_rf_predict(const float* X, const unsigned* nodes,
                                   int n_leaves, int T, int C,
                                   hipStream_t stream) {
   // TCSDN_RF_MODE (read per launch) picks the large-batch kernel:
-  //   5  streaming kernel (lanes advance through trees and rows on their
-  //      own), node table staged in LDS, 1024-thread blocks — THE DEFAULT
-  //      from RF_STREAM_MIN_ROWS rows up when the table fits
+  //   6  streaming kernel (lanes advance through trees and rows on their
+  //      own), node table staged in LDS, 1024-thread blocks, TWO rows per
+  //      lane; needs the table and two sets of feature rows in LDS, else it
+  //      runs as mode 5
+  //   5  the same with one row per lane; a table too big for LDS runs as
+  //      mode 4
   //   4  streaming kernel, node table in L2, 256-thread blocks
   //   2  row-per-lane, features in LDS (pitch 13, one ds_read per node),
   //      node table in L2 — the default between the wave-per-row cutover
@@ -527,17 +597,24 @@ extern "C" void launch_rf_predict(const float* X, const unsigned* nodes,
   //      occupancy next to a big forest)
   //   0  row-per-lane, features in registers (sel12 select tree), nodes in
   //      LDS when they fit
-  // Set explicitly, 4 and 5 apply at every n (how the tests reach the
+  // THE DEFAULT is mode 6 from RF_STREAM2_MIN_ROWS rows up and mode 5 from
+  // RF_STREAM_MIN_ROWS up, each when its tables fit in LDS (mode 6 falls
+  // back to 5, mode 5 to 2), and mode 2 below.
+  // Set explicitly, 4, 5 and 6 apply at every n (how the tests reach the
   // streaming kernel with small inputs); 0..2 only above the cutover.
   // Measured on the 100-tree reference forest, 10M rows: modes 0/1/2 =
   // 2.09/2.12/2.60 Gflows/s (profiles/kernel_opt_r02.md), modes 4/5 against
-  // mode 2 in profiles/rf_predict_stream.md.
+  // mode 2 in profiles/rf_predict_stream.md, the feature-major rows and
+  // mode 6 in profiles/rf_predict_stream2.md.
   const size_t snode_bytes = (size_t)(n_nodes + 2) * sizeof(uint2);
-  const bool snodes_fit = snode_bytes + 1024 * 13 * sizeof(float) <= 160 * 1024;
+  const size_t feat_set = 1024 * 13 * sizeof(float);  // one row per thread of a block
+  const bool snodes_fit = snode_bytes + feat_set <= 160 * 1024;
+  const bool snodes_fit2 = snode_bytes + 2 * feat_set <= 160 * 1024;
   const char* mode_env = getenv("TCSDN_RF_MODE");
   int mode = mode_env ? atoi(mode_env)
-                      : (n >= RF_STREAM_MIN_ROWS && snodes_fit ? 5 : 2);
-  const bool force_stream = mode_env && (mode == 4 || mode == 5);
+             : n >= RF_STREAM2_MIN_ROWS && snodes_fit2 ? 6
+             : n >= RF_STREAM_MIN_ROWS && snodes_fit ? 5 : 2;
+  const bool force_stream = mode_env && (mode == 4 || mode == 5 || mode == 6);
   if (n <= 131072 && !force_stream) {  // wave-per-row fills the chip at serve batch sizes
     dim3 wgrid((unsigned)((n + 3) / 4));
 #define RFW_CASE(CV)                                                        \
@@ -553,49 +630,56 @@ extern "C" void launch_rf_predict(const float* X, const unsigned* nodes,
     }
 #undef RFW_CASE
   }
-  if ((mode == 4 || mode == 5) && n > 0 && n_nodes > 0 && n_leaves > 0 && T > 0) {
+  if (mode >= 4 && mode <= 6 && n > 0 && n_nodes > 0 && n_leaves > 0 && T > 0) {
     // One row range per resident wave: the drain tail, the last rows of a
     // range running on a thinning wave, is then about one row in ~19 at
-    // 10M rows.  Below 64 rows per wave there is nothing to refill, so
-    // small batches get fewer waves instead.
+    // 10M rows.  Below one row per slot of a wave (64, or 128 with two rows
+    // per lane) there is nothing to refill, so small batches get fewer
+    // waves instead.
     // TCSDN_RF_STREAM_RANGE overrides the rows per wave, and
-    // TCSDN_RF_STREAM_REFILL the count of parked lanes that starts a pass.
-    // Mode 5 stages the node table in LDS beside the feature rows (one
-    // 1024-thread block per CU); a table too big for that runs as mode 4.
-    const bool lds_nodes = mode == 5 && snodes_fit;
+    // TCSDN_RF_STREAM_REFILL the count of parked slots that starts a pass.
+    // Modes 5 and 6 stage the node table in LDS beside the feature rows
+    // (one 1024-thread block per CU); a table too big for two sets of rows
+    // runs as mode 5, one too big for that as mode 4.
+    const bool two_rows = mode == 6 && snodes_fit2;
+    const bool lds_nodes = mode != 4 && snodes_fit;
+    const int slots = two_rows ? 2 * WAVE : WAVE;  // per wave
     const int sb = lds_nodes ? 1024 : 256;
     const long long resident = 256ll * (lds_nodes ? 16 : 32);
     long long range = (n + resident - 1) / resident;
     if (const char* e = getenv("TCSDN_RF_STREAM_RANGE")) range = atoll(e);
-    if (range < WAVE) range = WAVE;
+    if (range < slots) range = slots;
     if (range > (1ll << 30)) range = 1ll << 30;
-    int refill = 16;
+    int refill = two_rows ? RF_STREAM_REFILL2 : 16;
     if (const char* e = getenv("TCSDN_RF_STREAM_REFILL")) refill = atoi(e);
     if (refill < 1) refill = 1;
-    if (refill > WAVE) refill = WAVE;
+    if (refill > slots) refill = slots;
     const long long waves = (n + range - 1) / range;
     dim3 sgrid((unsigned)((waves + sb / WAVE - 1) / (sb / WAVE)));
-    size_t slds = (size_t)sb * 13 * sizeof(float) + (lds_nodes ? snode_bytes : 0);
-#define RFS_LAUNCH(CV, LN)                                                   \
+    size_t slds = (two_rows ? 2 * feat_set : (size_t)sb * 13 * sizeof(float)) +
+                  (lds_nodes ? snode_bytes : 0);
+#define RFS_LAUNCH(CV, LN, RV)                                               \
   do {                                                                       \
     if (LN) {                                                                \
       static bool once = false;                                              \
       if (!once) {                                                           \
-        hipFuncSetAttribute(                                                 \
-            reinterpret_cast<const void*>(&rf_predict_stream_kernel<CV, LN>),\
-            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);         \
+        hipFuncSetAttribute(reinterpret_cast<const void*>(                   \
+                                &rf_predict_stream_kernel<CV, LN, RV>),      \
+                            hipFuncAttributeMaxDynamicSharedMemorySize,      \
+                            160 * 1024);                                     \
         once = true;                                                         \
       }                                                                      \
     }                                                                        \
-    hipLaunchKernelGGL((rf_predict_stream_kernel<CV, LN>), sgrid, dim3(sb),  \
-                       slds, stream, X,                                      \
+    hipLaunchKernelGGL((rf_predict_stream_kernel<CV, LN, RV>), sgrid,        \
+                       dim3(sb), slds, stream, X,                            \
                        reinterpret_cast<const uint2*>(snodes), leaf_proba,   \
                        out, n, (int)range, n_nodes, n_leaves, T, refill);    \
   } while (0)
 #define RFS_CASE(CV)                                                         \
   case CV:                                                                   \
-    if (lds_nodes) RFS_LAUNCH(CV, true);                                     \
-    else RFS_LAUNCH(CV, false);                                              \
+    if (two_rows) RFS_LAUNCH(CV, true, 2);                                   \
+    else if (lds_nodes) RFS_LAUNCH(CV, true, 1);                             \
+    else RFS_LAUNCH(CV, false, 1);                                           \
     return;
     switch (C) {
       RFS_CASE(2) RFS_CASE(3) RFS_CASE(4) RFS_CASE(5) RFS_CASE(6) RFS_CASE(7)

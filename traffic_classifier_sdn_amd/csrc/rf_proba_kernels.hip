@@ -99,8 +99,10 @@ __launch_bounds__(256) __global__ void rf_scores_wave_kernel(
 
 // ---------------------------------------------------------------------------
 // Row-per-lane (large batches): the mode-2 placement of rf_predict_kernel —
-// each lane's 12 features in LDS at pitch 13 (gcd(13,32) = 1: a 32-lane
-// group's runtime feature picks land on distinct banks), node table in L2.
+// each lane's 12 features in LDS at pitch 13, node table in L2.  (gcd(13,32)
+// = 1 keeps a 32-lane group on distinct banks only while its lanes pick the
+// same feature, which lanes at different depths of a tree do not: the pick
+// does pay bank conflicts, see rf_predict_kernel.)
 //
 // Output: labels and conf are one dword per lane, coalesced as they are.  A
 // lane also stores its own C probabilities: C dword stores of stride 4C
