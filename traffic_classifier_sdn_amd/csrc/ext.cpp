@@ -45,6 +45,11 @@ int launch_ensemble_vote(const EnsembleArgs*, float*, int*, float*, long long,
 void launch_svc_predict(const float*, const float*, const float*,
                         const unsigned char*, const float*, int*, long long,
                         int, int, float, hipStream_t);
+int launch_svc_decision(const float*, const float*, const float*,
+                        const unsigned char*, const float*, double*, long long,
+                        int, int, float, hipStream_t);
+int launch_svc_couple(const double*, const double*, const double*, float*,
+                      int*, float*, long long, int, hipStream_t);
 void launch_knn_topk(const float*, const float*, const unsigned char*, float*,
                      int*, int*, long long, long long, int, int, long long,
                      hipStream_t);
@@ -328,6 +333,64 @@ static torch::Tensor svc_predict(torch::Tensor X, torch::Tensor SV,
                      intercept.data_ptr<float>(), out.data_ptr<int>(), n, nsv,
                      C, (float)gamma, cur_stream());
   return out;
+}
+
+// SVC class probabilities (svc_proba_kernels.hip).  The decision kernels
+// index SV, dual, svclass and intercept by nsv and C alone, so every extent
+// is checked here.
+static torch::Tensor svc_decision(torch::Tensor X, torch::Tensor SV,
+                                  torch::Tensor dual, torch::Tensor svclass,
+                                  torch::Tensor intercept, double gamma) {
+  CHECK_IN(X, torch::kFloat32);
+  CHECK_IN(SV, torch::kFloat32);
+  CHECK_IN(dual, torch::kFloat32);
+  CHECK_IN(svclass, torch::kUInt8);
+  CHECK_IN(intercept, torch::kFloat32);
+  TORCH_CHECK(X.dim() == 2 && X.size(1) == 12, "X must be (n,12)");
+  TORCH_CHECK(SV.dim() == 2 && SV.size(1) == 12, "SV must be (nsv,12)");
+  TORCH_CHECK(dual.dim() == 2, "dual must be (C-1,nsv)");
+  const long long n = X.size(0);
+  const int64_t nsv = SV.size(0);
+  const int64_t C = dual.size(0) + 1;
+  TORCH_CHECK(C >= 2 && C <= 6, "svc_decision supports 2..6 classes, got ", C);
+  TORCH_CHECK(nsv <= INT32_MAX, "too many support vectors");
+  const int64_t npair = C * (C - 1) / 2;
+  TORCH_CHECK(dual.size(1) == nsv, "dual must be (C-1,nsv)");
+  TORCH_CHECK(svclass.numel() == nsv, "svclass must have one entry per SV");
+  TORCH_CHECK(intercept.numel() == npair, "intercept must have C(C-1)/2 entries");
+  auto out = torch::empty({n, npair}, X.options().dtype(torch::kFloat64));
+  const int rc = launch_svc_decision(
+      X.data_ptr<float>(), SV.data_ptr<float>(), dual.data_ptr<float>(),
+      svclass.data_ptr<unsigned char>(), intercept.data_ptr<float>(),
+      out.data_ptr<double>(), n, (int)nsv, (int)C, (float)gamma, cur_stream());
+  TORCH_CHECK(rc == 0, "svc_decision: no kernel for ", C, " classes");
+  return out;
+}
+
+// Returns (proba [n,C] f32, idx [n] i32, conf [n] f32).
+static std::vector<torch::Tensor> svc_couple(torch::Tensor dec,
+                                             torch::Tensor probA,
+                                             torch::Tensor probB, int64_t C) {
+  CHECK_IN(dec, torch::kFloat64);
+  CHECK_IN(probA, torch::kFloat64);
+  CHECK_IN(probB, torch::kFloat64);
+  TORCH_CHECK(C >= 2 && C <= 6, "svc_couple supports 2..6 classes, got ", C);
+  const int64_t npair = C * (C - 1) / 2;
+  TORCH_CHECK(dec.dim() == 2 && dec.size(1) == npair,
+              "dec must be (n,C(C-1)/2)");
+  TORCH_CHECK(probA.numel() == npair && probB.numel() == npair,
+              "probA and probB must have C(C-1)/2 entries");
+  const long long n = dec.size(0);
+  auto f32 = dec.options().dtype(torch::kFloat32);
+  auto proba = torch::empty({n, C}, f32);
+  auto idx = torch::empty({n}, dec.options().dtype(torch::kInt32));
+  auto conf = torch::empty({n}, f32);
+  const int rc = launch_svc_couple(
+      dec.data_ptr<double>(), probA.data_ptr<double>(),
+      probB.data_ptr<double>(), proba.data_ptr<float>(), idx.data_ptr<int>(),
+      conf.data_ptr<float>(), n, (int)C, cur_stream());
+  TORCH_CHECK(rc == 0, "svc_couple: no kernel for ", C, " classes");
+  return {proba, idx, conf};
 }
 
 static std::vector<torch::Tensor> knn_topk(torch::Tensor Q, torch::Tensor R,
@@ -676,6 +739,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ensemble_vote", &ensemble_vote,
         "soft vote over member probabilities: (avg | empty, labels, conf)");
   m.def("svc_predict", &svc_predict, "RBF Gram + OVO vote");
+  m.def("svc_decision", &svc_decision, "RBF Gram + OVO decision values (f64)");
+  m.def("svc_couple", &svc_couple,
+        "Platt sigmoids + pairwise coupling: (proba, idx, conf)");
   m.def("knn_topk", &knn_topk, "brute-force top-k (+fused vote)");
   m.def("knn_topk_mfma", &knn_topk_mfma, "MFMA distance-GEMM top-k (+fused vote)",
         py::arg("Q"), py::arg("R"), py::arg("cmean"), py::arg("ry"),

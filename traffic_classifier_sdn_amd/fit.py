@@ -4,6 +4,7 @@ SURVEY.md §2.1 C9 / §3.4).
 
     python -m traffic_classifier_sdn_amd.fit [--algos all] [--out models]
         [--device cuda|cpu] [--sklearn-pickles] [--test-size 0.5] [--seed 101]
+        [--svc-probability]
 
 Per algorithm it reproduces the notebook protocol exactly: load the shipped
 per-class CSVs, dropna, drop the 4 cumulative columns (12 model features),
@@ -89,9 +90,12 @@ def fit_one(
     yte: np.ndarray,
     device: Optional[str],
     sharded: bool,
+    svc_probability: bool = False,
 ) -> Dict:
     ctor, _ = ALGOS[algo]
     model = ctor(device)
+    if algo == "svm" and svc_probability:
+        model = SVC(device=device, probability=True)
     rank = dist.rank() if dist.is_initialized() else 0
     # row shard for this rank (deterministic contiguous split)
     if sharded:
@@ -147,6 +151,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                          "true 6-class fit — the reference's quake CSV is not "
                          "shipped; accuracies are then against the synthetic "
                          "6-class split, not the published 5-class-real rows")
+    ap.add_argument("--svc-probability", action="store_true",
+                    help="fit the SVC with probability=True: 5-fold cross-validated "
+                         "Platt sigmoids per class pair, written into its checkpoint, "
+                         "so that 'svm --confidence' and an ensemble can use it "
+                         "(not with a sharded fit)")
     args = ap.parse_args(argv)
 
     # torchrun-aware: initialize the group if launched with a WORLD_SIZE
@@ -160,6 +169,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             torch.cuda.set_device(dist.env_local_rank())
     sharded = dist.is_initialized() and dist.world_size() > 1
     rank = dist.rank() if dist.is_initialized() else 0
+    if args.svc_probability and sharded:
+        print("ERROR: --svc-probability has no sharded fit: run it on one rank", file=sys.stderr)
+        return 2
 
     if args.with_synth_quake:
         from .utils.datasets import load_six_class_dataset
@@ -178,7 +190,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     os.makedirs(args.out, exist_ok=True) if rank == 0 else None
     ok = True
     for algo in algos:
-        res = fit_one(algo, Xtr, ytr, Xte, yte, args.device, sharded)
+        res = fit_one(algo, Xtr, ytr, Xte, yte, args.device, sharded,
+                      svc_probability=args.svc_probability)
         model = res.pop("_model")
         if rank == 0:
             fname = ALGOS[algo][1]

@@ -9,7 +9,7 @@ from .kmeans import KMeans
 from .kneighbors import KNeighborsClassifier
 from .logistic import LogisticRegression
 from .random_forest import RandomForestClassifier
-from .svc import SVC
+from .svc import SVC, CalibratedSVC
 
 _KIND_TO_CLASS = {
     "logistic": LogisticRegression,
@@ -54,6 +54,7 @@ def load_model(path: str, device: Optional[str] = None) -> Estimator:
 
 
 __all__ = [
+    "CalibratedSVC",
     "Estimator",
     "GaussianNB",
     "KMeans",

@@ -244,6 +244,161 @@ def svc_predict(
     return svc_vote(dec, int(n_support.numel()))
 
 
+def svc_decision(
+    X: torch.Tensor,
+    SV: torch.Tensor,
+    dual_coef: torch.Tensor,
+    intercept: torch.Tensor,
+    n_support: torch.Tensor,
+    gamma: float,
+    svclass: torch.Tensor = None,
+) -> torch.Tensor:
+    """f64 [n, C(C-1)/2] one-vs-one decision values, pair order as
+    ``svc_ovo_decision``.  Everything is cast up, so f64 rows give the f64
+    decision function."""
+    Xd = X.double()
+    K = rbf_kernel(Xd, SV.double(), gamma)
+    return svc_ovo_decision(K, dual_coef.double(), intercept.double(), n_support)
+
+
+def svc_couple(
+    dec: torch.Tensor,
+    probA: torch.Tensor,
+    probB: torch.Tensor,
+    n_classes: int,
+    with_margin: bool = False,
+):
+    """Class probabilities from one-vs-one decision values: a Platt sigmoid
+    per pair, coupled by the method of Wu, Lin and Weng.  A transcription of
+    libsvm (sigmoid_predict, svm_predict_probability, multiclass_probability)
+    in f64 and in its operation order, rows side by side; every row leaves
+    the iteration at its own sweep, as it would alone.
+
+    Returns (proba f64[n,C], idx int32[n], conf f64[n]): ``idx`` is
+    ``svc_vote`` of the same decisions and ``conf`` the coupled probability
+    of that voted class, which need not be the row's largest.  With
+    ``with_margin`` a fourth value: per row, the smallest |max_error - eps|
+    over the stopping tests it went through, i.e. how far the row stayed from
+    stopping one sweep earlier or later."""
+    k = int(n_classes)
+    dec = dec.double()
+    n = dec.shape[0]
+    A = probA.double().to(dec.device)
+    B = probB.double().to(dec.device)
+    # sigmoid_predict, both branches: exp(-|fApB|) is the argument of each
+    fApB = dec * A + B
+    e = torch.exp(-fApB.abs())
+    s = torch.where(fApB >= 0, e / (1.0 + e), 1.0 / (1 + e))
+    s = torch.clamp(s, 1e-7, 1 - 1e-7)
+    r = [[None] * k for _ in range(k)]
+    p = 0
+    for i in range(k):
+        for j in range(i + 1, k):
+            r[i][j] = s[:, p]
+            r[j][i] = 1 - s[:, p]
+            p += 1
+    zero = torch.zeros(n, dtype=torch.float64, device=dec.device)
+    Q = [[None] * k for _ in range(k)]
+    for t in range(k):
+        q = zero.clone()
+        for j in range(t):
+            q = q + r[j][t] * r[j][t]
+            Q[t][j] = Q[j][t]
+        for j in range(t + 1, k):
+            q = q + r[j][t] * r[j][t]
+            Q[t][j] = -r[j][t] * r[t][j]
+        Q[t][t] = q
+    pr = [torch.full((n,), 1.0 / k, dtype=torch.float64, device=dec.device) for _ in range(k)]
+    eps = 0.005 / k
+    active = torch.ones(n, dtype=torch.bool, device=dec.device)
+    margin = torch.full((n,), float("inf"), dtype=torch.float64, device=dec.device)
+    for _ in range(max(100, k)):
+        Qp = []
+        pQp = zero.clone()
+        for t in range(k):
+            a = zero.clone()
+            for j in range(k):
+                a = a + Q[t][j] * pr[j]
+            Qp.append(a)
+            pQp = pQp + pr[t] * a
+        max_error = zero.clone()
+        for t in range(k):
+            max_error = torch.maximum(max_error, (Qp[t] - pQp).abs())
+        margin = torch.where(active, torch.minimum(margin, (max_error - eps).abs()), margin)
+        active = active & ~(max_error < eps)
+        if not bool(active.any()):
+            break
+        new = list(pr)
+        for t in range(k):
+            diff = (-Qp[t] + pQp) / Q[t][t]
+            new[t] = new[t] + diff
+            pQp = (pQp + diff * (diff * Q[t][t] + 2 * Qp[t])) / (1 + diff) / (1 + diff)
+            for j in range(k):
+                Qp[j] = (Qp[j] + diff * Q[t][j]) / (1 + diff)
+                new[j] = new[j] / (1 + diff)
+        pr = [torch.where(active, new[t], pr[t]) for t in range(k)]
+    proba = torch.stack(pr, dim=1)
+    idx = svc_vote(dec, k)
+    conf = torch.gather(proba, 1, idx.long().unsqueeze(1)).squeeze(1)
+    if with_margin:
+        return proba, idx, conf, margin
+    return proba, idx, conf
+
+
+def platt_fit(dec: torch.Tensor, is_first: torch.Tensor) -> Tuple[float, float]:
+    """(A, B) of the sigmoid P(first class | dec) = 1 / (1 + exp(A*dec + B))
+    for one class pair: libsvm's sigmoid_train.  ``is_first`` marks the rows
+    of the pair's first class, the one a positive decision votes for.
+    Prior-smoothed targets, Newton with a backtracking line search
+    (max_iter 100, min_step 1e-10, sigma 1e-12, eps 1e-5).  Runs on the host
+    in f64: a fit-time step over one pair's rows."""
+    d = dec.detach().double().cpu().ravel()
+    first = is_first.detach().cpu().ravel().to(torch.bool)
+    prior1 = float(first.sum())
+    prior0 = float(first.numel()) - prior1
+    max_iter, min_step, sigma, eps = 100, 1e-10, 1e-12, 1e-5
+    hi = (prior1 + 1.0) / (prior1 + 2.0)
+    lo = 1.0 / (prior0 + 2.0)
+    t = torch.where(first, torch.tensor(hi, dtype=torch.float64), torch.tensor(lo, dtype=torch.float64))
+
+    def objective(a: float, b: float) -> float:
+        f = d * a + b
+        lg = torch.log1p(torch.exp(-f.abs()))  # log(1+exp(-|f|)), both branches
+        return float(torch.where(f >= 0, t * f + lg, (t - 1) * f + lg).sum())
+
+    A, B = 0.0, float(np.log((prior0 + 1.0) / (prior1 + 1.0)))
+    fval = objective(A, B)
+    for _ in range(max_iter):
+        f = d * A + B
+        e = torch.exp(-f.abs())
+        p = torch.where(f >= 0, e / (1.0 + e), 1.0 / (1.0 + e))
+        q = torch.where(f >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+        d2 = p * q
+        h11 = sigma + float((d * d * d2).sum())
+        h22 = sigma + float(d2.sum())
+        h21 = float((d * d2).sum())
+        d1 = t - p
+        g1 = float((d * d1).sum())
+        g2 = float(d1.sum())
+        if abs(g1) < eps and abs(g2) < eps:
+            break
+        det = h11 * h22 - h21 * h21
+        dA = -(h22 * g1 - h21 * g2) / det
+        dB = -(-h21 * g1 + h11 * g2) / det
+        gd = g1 * dA + g2 * dB
+        step = 1.0
+        while step >= min_step:
+            newA, newB = A + step * dA, B + step * dB
+            newf = objective(newA, newB)
+            if newf < fval + 0.0001 * step * gd:
+                A, B, fval = newA, newB, newf
+                break
+            step /= 2.0
+        if step < min_step:  # line search fails: keep the last iterate
+            break
+    return A, B
+
+
 # ----------------------------------------------------------------------
 # Random forest predict (N4)
 # ----------------------------------------------------------------------

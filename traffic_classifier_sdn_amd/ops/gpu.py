@@ -195,6 +195,50 @@ def svc_predict(
     )
 
 
+# ----------------------------------------------------------------------
+# SVC class probabilities (csrc/svc_proba_kernels.hip)
+# ----------------------------------------------------------------------
+
+platt_fit = _cpu.platt_fit  # cold: a fit-time Newton iteration on the host
+
+
+def svc_decision(
+    X: torch.Tensor,
+    SV: torch.Tensor,
+    dual_coef: torch.Tensor,
+    intercept: torch.Tensor,
+    n_support: torch.Tensor,
+    gamma: float,
+    svclass: torch.Tensor = None,
+) -> torch.Tensor:
+    """f64 [n, C(C-1)/2] one-vs-one decision values, accumulated exactly as
+    ``svc_predict`` accumulates them, so their signs give its votes."""
+    if X.shape[1] != 12:
+        return _cpu.svc_decision(X, SV, dual_coef, intercept, n_support, gamma, svclass)
+    if svclass is None:
+        # static per model; callers on the hipGraph path precompute it
+        svclass = torch.repeat_interleave(
+            torch.arange(n_support.numel(), device=X.device), n_support.to(X.device)
+        ).to(torch.uint8)
+    return _ext.svc_decision(
+        _f32(X), _f32_cached(SV), _f32_cached(dual_coef), svclass.contiguous(),
+        _f32_cached(intercept), float(gamma)
+    )
+
+
+def svc_couple(
+    dec: torch.Tensor, probA: torch.Tensor, probB: torch.Tensor, n_classes: int
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(proba[n,C] f32, idx[n] int32, conf[n] f32): Platt sigmoids of the
+    decision values coupled as libsvm couples them, the one-vs-one vote of
+    the same decisions, and the coupled probability of the voted class.
+    A CalibratedSVC keeps its sigmoids as f64 device tensors, so nothing is
+    converted or copied here and a captured graph replays the kernel alone."""
+    return _ext.svc_couple(
+        _f64(dec), _f64(probA.to(dec.device)), _f64(probB.to(dec.device)), int(n_classes)
+    )
+
+
 def rf_hist(bins: torch.Tensor, y: torch.Tensor, nid: torch.Tensor, n_nodes: int,
             n_classes: int, fsel: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Per-node per-feature class histograms.  With ``fsel`` (u8

@@ -151,16 +151,25 @@ def params_from_shadow(obj: ShadowObject) -> Dict[str, Any]:
             "n_iter": int(obj.n_iter_),
         }
     if name == "SVC":
-        return {
+        params = {
             "kind": "svc",
             "classes": _labels_to_str(obj.classes_),
             "support_vectors": np.asarray(obj.support_vectors_, dtype=np.float64),
-            "dual_coef": np.asarray(obj.dual_coef_, dtype=np.float64),
+            # libsvm's own layout: the private pair, which differs from the
+            # public one (by sign) only in a two-class model
+            "dual_coef": np.asarray(getattr(obj, "_dual_coef_", obj.dual_coef_), dtype=np.float64),
             "intercept": np.asarray(obj._intercept_, dtype=np.float64),
             "n_support": np.asarray(obj._n_support, dtype=np.int64),
             "gamma": float(obj._gamma),
             "support": np.asarray(obj.support_, dtype=np.int64),
         }
+        # Platt sigmoids of an SVC(probability=True); both are empty otherwise
+        probA = getattr(obj, "_probA", getattr(obj, "probA_", None))
+        probB = getattr(obj, "_probB", getattr(obj, "probB_", None))
+        if probA is not None and probB is not None and np.size(probA) > 0 and np.size(probB) > 0:
+            params["probA"] = np.asarray(probA, dtype=np.float64).ravel()
+            params["probB"] = np.asarray(probB, dtype=np.float64).ravel()
+        return params
     if name == "KNeighborsClassifier":
         return {
             "kind": "kneighbors",
@@ -317,18 +326,34 @@ def params_to_sklearn(params: Dict[str, Any]):
         est = SkSVC(kernel="rbf", gamma=gamma)
         est.classes_ = classes
         est.support_vectors_ = SV
-        support = np.asarray(params.get("support", np.arange(SV.shape[0])))
+        support = np.asarray(params.get("support", ()))
+        if support.size != SV.shape[0]:
+            # a checkpoint without its training-row indices (the shipped one
+            # stores none): libsvm takes the NUMBER of support vectors from
+            # this array, and with an empty one every decision value is NaN
+            support = np.arange(SV.shape[0])
         est.support_ = np.ascontiguousarray(support, dtype=np.int32)
         est._n_support = n_support
-        # sklearn negates the public dual/intercept for binary problems
-        # (sklearn/svm/_base.py fit); params hold the public layout
+        est.class_weight_ = np.ones(len(classes), dtype=np.float64)
+        # params hold libsvm's own layout (a positive decision votes for the
+        # pair's FIRST class), which sklearn keeps in the private attributes;
+        # its public dual/intercept are negated for binary problems
+        # (sklearn/svm/_base.py fit).  The other way round, an exported
+        # two-class model predicted the opposite class on every row.
         binary = len(classes) == 2
-        est.dual_coef_ = dual
-        est._dual_coef_ = -dual if binary else dual
-        est.intercept_ = intercept
-        est._intercept_ = -intercept if binary else intercept
-        est._probA = np.empty(0, dtype=np.float64)
-        est._probB = np.empty(0, dtype=np.float64)
+        est._dual_coef_ = dual
+        est.dual_coef_ = -dual if binary else dual
+        est._intercept_ = intercept
+        est.intercept_ = -intercept if binary else intercept
+        if np.size(params.get("probA", ())) > 0 and np.size(params.get("probB", ())) > 0:
+            # the sigmoids apply to libsvm's own decision values, which are
+            # the ones the private attributes above reproduce
+            est.probability = True
+            est._probA = np.ascontiguousarray(params["probA"], dtype=np.float64).ravel()
+            est._probB = np.ascontiguousarray(params["probB"], dtype=np.float64).ravel()
+        else:
+            est._probA = np.empty(0, dtype=np.float64)
+            est._probB = np.empty(0, dtype=np.float64)
         est._gamma = gamma
         est._sparse = False
         est.shape_fit_ = (int(params.get("n_fit_rows", SV.shape[0])), SV.shape[1])
