@@ -517,3 +517,15 @@ def test_knn_gpu_tolerates_absurd_magnitudes():
         Q[3] = np.nan
         pred = m.predict_index(Q).cpu()
         assert int(pred.min()) >= 0 and int(pred.max()) < 6, (n_ref, approx)
+
+
+@pytest.mark.gpu
+def test_knn_topk_rejects_a_k_without_kernel():
+    """k = 9 passes the binding's k <= 32 check but has no instantiation:
+    an error, not a tensor that no kernel wrote."""
+    from traffic_classifier_sdn_amd.ops.gpu import _ext
+
+    Q = torch.zeros(4, 12, device="cuda")
+    R = torch.zeros(16, 12, device="cuda")
+    with pytest.raises(RuntimeError, match="no kernel for k = 9"):
+        _ext.knn_topk(Q, R, None, 9, 0, 0)

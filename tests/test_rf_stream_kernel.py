@@ -357,3 +357,43 @@ def test_pack_wide_forests_have_no_pure_leaves():
         shift = packed["snodes"][:-2, 1][leaf] & 63
         assert bool((shift != 61).all()) == pure
         assert bool((shift == 61).all()) == (not pure)
+
+
+# ----------------------------------------------------------------------
+# class counts at the edges of the launcher's dispatch
+# ----------------------------------------------------------------------
+
+
+@needs_gpu
+@pytest.mark.gpu
+def test_twelve_classes_below_the_wave_cutover(monkeypatch):
+    """The wave-per-row kernel exists for 2..8 classes only: 300 rows of a
+    12-class forest fall through to the row-per-lane kernel and get the
+    oracle's labels."""
+    for k in ("TCSDN_RF_MODE", "TCSDN_RF_STREAM_RANGE", "TCSDN_RF_STREAM_REFILL"):
+        monkeypatch.delenv(k, raising=False)
+    rng = np.random.default_rng(12)
+    forest = oc.rf_flatten([_tree(rng, 12, 5, _mixed, min_depth=1) for _ in range(9)], 12)
+    X = _rows(300, 13)
+    ref = oc.rf_argmax(X, forest)
+    assert len(torch.unique(ref)) > 2
+    assert torch.equal(og.rf_argmax(X.cuda(), dict(forest)).cpu(), ref)
+
+
+@needs_gpu
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [8, 131073])  # wave-per-row and row-per-lane path
+def test_class_count_without_kernel_raises(monkeypatch, n):
+    """Nine classes have no instantiation on either path: an error, not a
+    label tensor that no kernel wrote."""
+    from traffic_classifier_sdn_amd.ops.gpu import _ext
+
+    monkeypatch.delenv("TCSDN_RF_MODE", raising=False)
+    rng = np.random.default_rng(9)
+    forest = oc.rf_flatten([_tree(rng, 9, 3, _mixed, min_depth=1)], 9)
+    packed = og.rf_pack(forest, "cuda")
+    assert packed["n_classes"] == 9 and packed["roots"].numel() == 1
+    X = torch.zeros(n, 12, device="cuda")
+    with pytest.raises(RuntimeError, match="no kernel for 9 classes"):
+        _ext.rf_predict(X, packed["nodes"], packed["snodes"], packed["roots"],
+                        packed["leaf_proba"], packed["n_leaves"], 9)

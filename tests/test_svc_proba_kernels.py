@@ -1,4 +1,4 @@
-"""SVC probability kernels (csrc/svc_proba_kernels.hip) against the CPU
+"""SVC decision and coupling kernels (csrc/svc_kernels.hip) against the CPU
 oracles in ops/cpu.py, then a calibrated SVC on the GPU and in a captured
 serve graph.
 
@@ -50,7 +50,7 @@ MODELS = os.path.join(REPO, "data", "ref_models")
 needs_gpu = pytest.mark.skipif(not torch.cuda.is_available(), reason="no GPU")
 
 ROWS = (1, 255, 256, 257, 1500)  # 256 rows per block: partial, full, second block
-CLASSES = (2, 3, 6)
+CLASSES = (2, 3, 4, 5, 6)
 # support vectors in all: below one wave, around the tile of 128, two tiles
 # and a partial one; 2 is one per class and only exists for two classes
 TOTALS = (2, 40, 127, 128, 129, 300)
@@ -136,11 +136,37 @@ def test_svc_decision_kernels(monkeypatch, C, mode):
             tag = f"C={C} mode={mode} nsv={total} n={n}"
             print(f"{tag}: max err / Sd {float((err / sd).max()):.3e} (bound {2.0 ** -16:.3e})")
             assert bool((err <= atol).all()), tag
-            if mode == WAVE:
-                # the label kernel at these sizes is the wave kernel too:
-                # the same accumulation, so the same votes, row for row
-                labels = og.svc_predict(X.cuda(), *dev, GAMMA)
-                assert torch.equal(oc.svc_vote(got, C), labels), tag
+            # the label kernel follows the forced mode too and accumulates
+            # as the decision kernel does: the same votes, row for row
+            labels = og.svc_predict(X.cuda(), *dev, GAMMA)
+            assert torch.equal(oc.svc_vote(got, C), labels), tag
+
+
+@needs_gpu
+@pytest.mark.gpu
+def test_svc_tiled_row_loop(monkeypatch):
+    """TCSDN_PROBA_BLOCKS=2 leaves the tiled kernels two blocks for the six
+    row tiles of 1500 rows: each block loops three times and the second ends
+    on the partial tile.  Same decisions as the uncapped launch, bit for
+    bit, within the oracle's bound, and the labels are their votes."""
+    og = _og()
+    monkeypatch.setenv("TCSDN_SVC_DEC_MODE", TILED)
+    monkeypatch.delenv("TCSDN_PROBA_BLOCKS", raising=False)
+    C, total, n = 6, 129, 1500
+    SV, dual, b, ns = _svc_params(C, total, seed=77)
+    dev = [t.cuda() for t in (SV, dual, b, ns)]
+    X = _rows(n, seed=78)
+    ref = _oracle_dec(X, SV, dual, b, ns)
+    uncapped = og.svc_decision(X.cuda(), *dev, GAMMA)
+    monkeypatch.setenv("TCSDN_PROBA_BLOCKS", "2")
+    got = og.svc_decision(X.cuda(), *dev, GAMMA)
+    labels = og.svc_predict(X.cuda(), *dev, GAMMA)
+    sd = _pair_sd(dual, ns)
+    err = (got.cpu() - ref).abs().max(dim=0).values
+    print(f"max err / Sd {float((err / sd).max()):.3e} (bound {2.0 ** -16:.3e})")
+    assert bool((err <= sd * 2.0 ** -16).all())
+    assert torch.equal(got, uncapped)
+    assert torch.equal(oc.svc_vote(got, C), labels)
 
 
 @needs_gpu

@@ -4,6 +4,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
+#include <type_traits>
+
 #define WAVE 64
 #define DEV __device__ __forceinline__
 
@@ -14,6 +17,26 @@ static inline int ts_grid(long long work, int block, int cap = 2048) {
   if (b > cap) b = cap;
   if (b < 1) b = 1;
   return (int)b;
+}
+
+// A grid cap that the environment variable `name` (read per launch) may
+// lower, never raise: tests set it so that small inputs make each block
+// loop over several row tiles and end on a partial one.
+static inline int env_block_cap(const char* name, int cap) {
+  if (const char* e = getenv(name)) {
+    const int v = atoi(e);
+    if (v >= 1 && v < cap) cap = v;
+  }
+  return cap;
+}
+
+// Host-side dispatch of a runtime integer onto a list of compile-time ones:
+// calls f(std::integral_constant<int, V>{}) for the V that equals v and
+// returns true, or calls nothing and returns false.  A launcher turns false
+// into its nonzero "nothing was launched" return.
+template <int... Vs, class F>
+static inline bool dispatch_int(int v, F&& f) {
+  return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
 }
 
 // 12-float feature row load: rows are 48 B, so every row is 16-B aligned
@@ -52,7 +75,9 @@ DEV unsigned long long wave_sum(unsigned long long x) {
 }
 
 // Forest traversal helpers shared by predict_kernels.hip and
-// rf_proba_kernels.hip.
+// rf_proba_kernels.hip.  The row-per-lane kernels (rf_predict_kernel,
+// rf_predict_stream_kernel, rf_scores_lane_kernel) keep their own walks: a
+// shared body cost them registers (profiles/kernel_bodies.md).
 
 // select v[f] for runtime f in [0,12) with compile-time register indices:
 // two levels — pick r = f&3 within each quad, then the quad q = f>>2.
@@ -79,4 +104,65 @@ DEV float sel12(const Row12& x, unsigned f) {
 DEV float vote_count(unsigned long long votes, int c) {
   return c * 10 + 10 <= 64 ? (float)(unsigned)((votes >> (c * 10)) & 1023ull)
                            : 0.f;
+}
+
+// Wave-per-row forest scores, the one statement of what rf_predict_wave_kernel
+// and rf_scores_wave_kernel compute: the wave's 64 lanes load the same row
+// and lane `lane` walks trees lane, lane+64, ...  Nodes are read from global
+// memory (the packed forest, tens of KB, stays L2-resident); per lane the
+// mixed leaves are added in tree order, then the packed counter and the C
+// partial sums are reduced with wave_sum.  On return
+//   sc[c] = acc[c] + pure count[c]
+// holds the row's class sums in lane 0 (other lanes hold partial values).
+template <int C>
+DEV void rf_wave_scores(const float* __restrict__ X, long long row, int lane,
+                        const uint2* __restrict__ nodes,
+                        const int* __restrict__ roots,
+                        const float* __restrict__ leaf_proba, int T,
+                        float (&sc)[C]) {
+  Row12 x = load_row12(X, row);  // broadcast load
+  float acc[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) acc[c] = 0.f;
+  unsigned long long votes = 0ull;  // 10-bit packed per-class pure counts
+  for (int t = lane; t < T; t += WAVE) {
+    int idx = roots[t];
+    while (true) {
+      uint2 node = nodes[idx];
+      unsigned feat = node.y & 0xffu;
+      if (feat >= 0xf0u) {
+        if (feat == 0xffu) {  // mixed leaf: read the distribution
+          int pr = (int)node.x * C;
+#pragma unroll
+          for (int c = 0; c < C; ++c) acc[c] += leaf_proba[pr + c];
+        } else {  // pure leaf: class in the low nibble
+          votes += 1ull << ((feat & 0xfu) * 10);
+        }
+        break;
+      }
+      float thr = __uint_as_float(node.x);
+      idx = (sel12(x, feat) <= thr) ? idx + 1 : (int)(node.y >> 8);
+    }
+  }
+  votes = wave_sum(votes);  // per-field sums stay < 1024: no cross-field carry
+#pragma unroll
+  for (int c = 0; c < C; ++c) sc[c] = wave_sum(acc[c]) + vote_count(votes, c);
+}
+
+// First-maximum argmax of the C scores (sklearn's tie rule; compared with >,
+// so a NaN never wins).  Only compile-time indices into sc[].
+struct ArgMax {
+  int idx;
+  float val;
+};
+
+template <int C>
+DEV ArgMax first_max(const float (&sc)[C]) {
+  float best = -INFINITY;
+  int bi = 0;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    if (sc[c] > best) { best = sc[c]; bi = c; }
+  }
+  return {bi, best};
 }

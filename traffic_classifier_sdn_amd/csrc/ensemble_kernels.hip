@@ -28,12 +28,7 @@
 // launch) caps it, so small inputs make each block loop over several row
 // tiles with a partial last one.
 static int proba_grid(long long n) {
-  int cap = 2048;
-  if (const char* e = getenv("TCSDN_PROBA_BLOCKS")) {
-    const int v = atoi(e);
-    if (v >= 1 && v < cap) cap = v;
-  }
-  return ts_grid(n, PROBA_BLOCK, cap);
+  return ts_grid(n, PROBA_BLOCK, env_block_cap("TCSDN_PROBA_BLOCKS", 2048));
 }
 
 // The softmax kernels read up to 2 * 8 * 12 f64 parameters from LDS per row.
@@ -290,10 +285,10 @@ __launch_bounds__(PROBA_BLOCK) __global__ void ensemble_vote_kernel(
 // of range (nothing is launched and the outputs stay unwritten: the caller
 // must turn that into an error).
 // ---------------------------------------------------------------------------
-#define PROBA_SWITCH(CVAR, CASE)                                            \
-  switch (CVAR) {                                                           \
-    CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)                 \
-  }
+template <class F>
+static int proba_dispatch(int C, F&& launch) {
+  return !dispatch_int<2, 3, 4, 5, 6, 7, 8>(C, launch);
+}
 
 extern "C" int launch_gnb_proba(const float* X, const double* theta,
                                 const double* inv_var, const double* cconst,
@@ -302,14 +297,11 @@ extern "C" int launch_gnb_proba(const float* X, const double* theta,
   if (C < 2 || C > 8) return 1;
   if (n <= 0) return 0;
   dim3 grid(proba_grid(n));
-#define GNBP_CASE(CV)                                                       \
-  case CV:                                                                  \
-    hipLaunchKernelGGL((gnb_proba_kernel<CV>), grid, dim3(PROBA_BLOCK), 0,  \
-                       stream, X, theta, inv_var, cconst, proba, n);        \
-    return 0;
-  PROBA_SWITCH(C, GNBP_CASE)
-#undef GNBP_CASE
-  return 1;
+  return proba_dispatch(C, [&](auto c) {
+    hipLaunchKernelGGL((gnb_proba_kernel<decltype(c)::value>), grid,
+                       dim3(PROBA_BLOCK), 0, stream, X, theta, inv_var, cconst,
+                       proba, n);
+  });
 }
 
 extern "C" int launch_linear_proba(const float* X, const float* W,
@@ -318,14 +310,10 @@ extern "C" int launch_linear_proba(const float* X, const float* W,
   if (C < 2 || C > 8) return 1;
   if (n <= 0) return 0;
   dim3 grid(proba_grid(n));
-#define LINP_CASE(CV)                                                       \
-  case CV:                                                                  \
-    hipLaunchKernelGGL((linear_proba_kernel<CV>), grid, dim3(PROBA_BLOCK),  \
-                       0, stream, X, W, b, proba, n);                       \
-    return 0;
-  PROBA_SWITCH(C, LINP_CASE)
-#undef LINP_CASE
-  return 1;
+  return proba_dispatch(C, [&](auto c) {
+    hipLaunchKernelGGL((linear_proba_kernel<decltype(c)::value>), grid,
+                       dim3(PROBA_BLOCK), 0, stream, X, W, b, proba, n);
+  });
 }
 
 extern "C" int launch_knn_vote_proba(const int* idx, const unsigned char* y,
@@ -334,15 +322,10 @@ extern "C" int launch_knn_vote_proba(const int* idx, const unsigned char* y,
   if (C < 2 || C > 8 || k < 1) return 1;
   if (n <= 0) return 0;
   dim3 grid(proba_grid(n));
-#define KNNP_CASE(CV)                                                       \
-  case CV:                                                                  \
-    hipLaunchKernelGGL((knn_vote_proba_kernel<CV>), grid,                   \
-                       dim3(PROBA_BLOCK), 0, stream, idx, y, proba, n, k,   \
-                       nr);                                                 \
-    return 0;
-  PROBA_SWITCH(C, KNNP_CASE)
-#undef KNNP_CASE
-  return 1;
+  return proba_dispatch(C, [&](auto c) {
+    hipLaunchKernelGGL((knn_vote_proba_kernel<decltype(c)::value>), grid,
+                       dim3(PROBA_BLOCK), 0, stream, idx, y, proba, n, k, nr);
+  });
 }
 
 // `avg` may be null: then only labels and conf are written.
@@ -358,18 +341,10 @@ extern "C" int launch_ensemble_vote(const EnsembleArgs* args, float* avg,
   }
   if (n <= 0) return 0;
   dim3 grid(proba_grid(n));
-#define ENS_CASE(CV)                                                        \
-  case CV:                                                                  \
-    if (avg)                                                                \
-      hipLaunchKernelGGL((ensemble_vote_kernel<CV, true>), grid,            \
-                         dim3(PROBA_BLOCK), 0, stream, *args, avg, labels,  \
-                         conf, n);                                          \
-    else                                                                    \
-      hipLaunchKernelGGL((ensemble_vote_kernel<CV, false>), grid,           \
-                         dim3(PROBA_BLOCK), 0, stream, *args, avg, labels,  \
-                         conf, n);                                          \
-    return 0;
-  PROBA_SWITCH(C, ENS_CASE)
-#undef ENS_CASE
-  return 1;
+  return proba_dispatch(C, [&](auto c) {
+    constexpr int CV = decltype(c)::value;
+    auto* kernel = avg ? ensemble_vote_kernel<CV, true> : ensemble_vote_kernel<CV, false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(PROBA_BLOCK), 0, stream, *args, avg,
+                       labels, conf, n);
+  });
 }

@@ -29,9 +29,9 @@ void launch_linear_argmax(const float*, const float*, const float*, int*,
                           long long, int, hipStream_t);
 void launch_kmeans_assign(const float*, const float*, int*, double*, double*,
                           double*, long long, int, int, hipStream_t);
-void launch_rf_predict(const float*, const unsigned*, const unsigned*,
-                       const int*, const float*, int*, long long, int, int,
-                       int, int, hipStream_t);
+int launch_rf_predict(const float*, const unsigned*, const unsigned*,
+                      const int*, const float*, int*, long long, int, int,
+                      int, int, hipStream_t);
 int launch_rf_scores(const float*, const unsigned*, const int*, const float*,
                      float*, int*, float*, long long, int, int, hipStream_t);
 int launch_gnb_proba(const float*, const double*, const double*,
@@ -42,17 +42,17 @@ int launch_knn_vote_proba(const int*, const unsigned char*, float*, long long,
                           int, long long, int, hipStream_t);
 int launch_ensemble_vote(const EnsembleArgs*, float*, int*, float*, long long,
                          int, hipStream_t);
-void launch_svc_predict(const float*, const float*, const float*,
-                        const unsigned char*, const float*, int*, long long,
-                        int, int, float, hipStream_t);
+int launch_svc_predict(const float*, const float*, const float*,
+                       const unsigned char*, const float*, int*, long long,
+                       int, int, float, hipStream_t);
 int launch_svc_decision(const float*, const float*, const float*,
                         const unsigned char*, const float*, double*, long long,
                         int, int, float, hipStream_t);
 int launch_svc_couple(const double*, const double*, const double*, float*,
                       int*, float*, long long, int, hipStream_t);
-void launch_knn_topk(const float*, const float*, const unsigned char*, float*,
-                     int*, int*, long long, long long, int, int, long long,
-                     hipStream_t);
+int launch_knn_topk(const float*, const float*, const unsigned char*, float*,
+                    int*, int*, long long, long long, int, int, long long,
+                    hipStream_t);
 void launch_knn_mfma(const float*, const float*, const float*,
                      const unsigned char*, float*, int*, float*, int*, int*,
                      long long, long long, int, int, int, long long, int,
@@ -169,12 +169,13 @@ static torch::Tensor rf_predict(torch::Tensor X, torch::Tensor nodes,
   const int n_nodes = nodes.size(0);
   const int T = roots.size(0);
   auto out = torch::empty({n}, X.options().dtype(torch::kInt32));
-  launch_rf_predict(X.data_ptr<float>(),
-                    reinterpret_cast<const unsigned*>(nodes.data_ptr<int>()),
-                    reinterpret_cast<const unsigned*>(snodes.data_ptr<int>()),
-                    roots.data_ptr<int>(), leaf_proba.data_ptr<float>(),
-                    out.data_ptr<int>(), n, n_nodes, (int)n_leaves, T, (int)C,
-                    cur_stream());
+  const int rc = launch_rf_predict(
+      X.data_ptr<float>(),
+      reinterpret_cast<const unsigned*>(nodes.data_ptr<int>()),
+      reinterpret_cast<const unsigned*>(snodes.data_ptr<int>()),
+      roots.data_ptr<int>(), leaf_proba.data_ptr<float>(), out.data_ptr<int>(),
+      n, n_nodes, (int)n_leaves, T, (int)C, cur_stream());
+  TORCH_CHECK(rc == 0, "rf_predict: no kernel for ", C, " classes");
   return out;
 }
 
@@ -328,14 +329,15 @@ static torch::Tensor svc_predict(torch::Tensor X, torch::Tensor SV,
   const int C = dual.size(0) + 1;
   TORCH_CHECK(C >= 2 && C <= 6, "svc kernel supports 2..6 classes");
   auto out = torch::empty({n}, X.options().dtype(torch::kInt32));
-  launch_svc_predict(X.data_ptr<float>(), SV.data_ptr<float>(),
-                     dual.data_ptr<float>(), svclass.data_ptr<unsigned char>(),
-                     intercept.data_ptr<float>(), out.data_ptr<int>(), n, nsv,
-                     C, (float)gamma, cur_stream());
+  const int rc = launch_svc_predict(
+      X.data_ptr<float>(), SV.data_ptr<float>(), dual.data_ptr<float>(),
+      svclass.data_ptr<unsigned char>(), intercept.data_ptr<float>(),
+      out.data_ptr<int>(), n, nsv, C, (float)gamma, cur_stream());
+  TORCH_CHECK(rc == 0, "svc_predict: no kernel for ", C, " classes");
   return out;
 }
 
-// SVC class probabilities (svc_proba_kernels.hip).  The decision kernels
+// SVC class probabilities (svc_kernels.hip).  The decision kernels
 // index SV, dual, svclass and intercept by nsv and C alone, so every extent
 // is checked here.
 static torch::Tensor svc_decision(torch::Tensor X, torch::Tensor SV,
@@ -414,9 +416,11 @@ static std::vector<torch::Tensor> knn_topk(torch::Tensor Q, torch::Tensor R,
     lab = torch::empty({nq}, Q.options().dtype(torch::kInt32));
     lab_ptr = lab.data_ptr<int>();
   }
-  launch_knn_topk(Q.data_ptr<float>(), R.data_ptr<float>(), ry_ptr,
-                  dist.data_ptr<float>(), idx.data_ptr<int>(), lab_ptr, nq, nr,
-                  (int)k, (int)C, idx_base, cur_stream());
+  const int rc = launch_knn_topk(
+      Q.data_ptr<float>(), R.data_ptr<float>(), ry_ptr, dist.data_ptr<float>(),
+      idx.data_ptr<int>(), lab_ptr, nq, nr, (int)k, (int)C, idx_base,
+      cur_stream());
+  TORCH_CHECK(rc == 0, "knn_topk: no kernel for k = ", k);
   if (ry.has_value()) return {dist, idx, lab};
   return {dist, idx};
 }

@@ -167,17 +167,10 @@ extern "C" void launch_logistic_grad(const double* X, const long long* y,
   const int block = 256;
   size_t bytes = (size_t)(C * 12 + C + (block / 64) * C * 13) * sizeof(double);
   dim3 grid(ts_grid(n, block));
-#define LG_CASE(CV)                                                         \
-  case CV:                                                                  \
-    hipLaunchKernelGGL((logistic_grad_kernel<CV>), grid, dim3(block),       \
-                       bytes, stream, X, y, W, b, grad, loss, n);           \
-    return;
-  switch (C) {
-    LG_CASE(2) LG_CASE(3) LG_CASE(4) LG_CASE(5) LG_CASE(6) LG_CASE(7)
-    LG_CASE(8) LG_CASE(12) LG_CASE(16)
-    default: break;
-  }
-#undef LG_CASE
+  dispatch_int<2, 3, 4, 5, 6, 7, 8, 12, 16>(C, [&](auto c) {
+    hipLaunchKernelGGL((logistic_grad_kernel<decltype(c)::value>), grid,
+                       dim3(block), bytes, stream, X, y, W, b, grad, loss, n);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -412,17 +405,10 @@ extern "C" void launch_rf_split(const int* hist, const unsigned char* fsel,
   const int block = 256;
   long long work = (long long)L * 12;
   dim3 grid((unsigned)((work + block - 1) / block));
-#define RFS_CASE(CV)                                                        \
-  case CV:                                                                  \
-    hipLaunchKernelGGL((rf_split_kernel<CV>), grid, dim3(block), 0, stream, \
-                       hist, fsel, best, cnt, L);                           \
-    return;
-  switch (C) {
-    RFS_CASE(2) RFS_CASE(3) RFS_CASE(4) RFS_CASE(5) RFS_CASE(6) RFS_CASE(7)
-    RFS_CASE(8) RFS_CASE(12) RFS_CASE(16)
-    default: break;
-  }
-#undef RFS_CASE
+  dispatch_int<2, 3, 4, 5, 6, 7, 8, 12, 16>(C, [&](auto c) {
+    hipLaunchKernelGGL((rf_split_kernel<decltype(c)::value>), grid, dim3(block),
+                       0, stream, hist, fsel, best, cnt, L);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -971,17 +957,10 @@ extern "C" void launch_rf_split_compact(const int* hist,
   const int block = 256;
   long long work = (long long)L * mf;
   dim3 grid((unsigned)((work + block - 1) / block));
-#define RFSC_CASE(CV)                                                       \
-  case CV:                                                                  \
-    hipLaunchKernelGGL((rf_split_compact_kernel<CV>), grid, dim3(block), 0, \
-                       stream, hist, fidx, best, cnt, L, mf);               \
-    return;
-  switch (C) {
-    RFSC_CASE(2) RFSC_CASE(3) RFSC_CASE(4) RFSC_CASE(5) RFSC_CASE(6)
-    RFSC_CASE(7) RFSC_CASE(8) RFSC_CASE(12) RFSC_CASE(16)
-    default: break;
-  }
-#undef RFSC_CASE
+  dispatch_int<2, 3, 4, 5, 6, 7, 8, 12, 16>(C, [&](auto c) {
+    hipLaunchKernelGGL((rf_split_compact_kernel<decltype(c)::value>), grid,
+                       dim3(block), 0, stream, hist, fidx, best, cnt, L, mf);
+  });
 }
 
 extern "C" void launch_rf_hist(const unsigned char* bins, const unsigned char* y,

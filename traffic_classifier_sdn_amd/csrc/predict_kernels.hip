@@ -1,4 +1,5 @@
-// CDNA4 predict kernels for the six estimators.
+// CDNA4 predict kernels for the estimators (the
+// SVC kernels, N2, are in svc_kernels.hip and follow the same rules).
 // Hand-written for gfx950: wave64 blocks, params staged in LDS, feature rows
 // as float4 vector loads, grid-stride over rows.  All label outputs use
 // first-maximum tie-breaking to match the sklearn semantics of the CPU
@@ -512,8 +513,8 @@ __global__ void rf_predict_stream_kernel(const float* __restrict__ X,
 // Small-batch variant: ONE WAVE PER ROW, trees split across lanes.  At
 // serve batch sizes the row-per-lane kernel runs a ~900-step serial
 // dependent-load chain per row on a mostly idle chip; here each lane walks
-// only ceil(T/64) trees and n waves fill the SIMDs.  Nodes are read from
-// global memory — the packed forest (tens of KB) stays L2-resident.
+// only ceil(T/64) trees and n waves fill the SIMDs.  The walk and the
+// reduction are rf_wave_scores (common.h), shared with rf_scores_wave_kernel.
 template <int C>
 __launch_bounds__(256) __global__ void rf_predict_wave_kernel(
     const float* __restrict__ X, const uint2* __restrict__ nodes,
@@ -523,43 +524,9 @@ __launch_bounds__(256) __global__ void rf_predict_wave_kernel(
   const long long row = (long long)blockIdx.x * (blockDim.x / WAVE) +
                         (threadIdx.x >> 6);
   if (row >= n) return;
-  Row12 x = load_row12(X, row);  // broadcast load
-  float acc[C];
-#pragma unroll
-  for (int c = 0; c < C; ++c) acc[c] = 0.f;
-  unsigned long long votes = 0ull;  // 10-bit packed per-class pure counts
-  for (int t = lane; t < T; t += WAVE) {
-    int idx = roots[t];
-    while (true) {
-      uint2 node = nodes[idx];
-      unsigned feat = node.y & 0xffu;
-      if (feat >= 0xf0u) {
-        if (feat == 0xffu) {
-          int pr = (int)node.x * C;
-#pragma unroll
-          for (int c = 0; c < C; ++c) acc[c] += leaf_proba[pr + c];
-        } else {
-          votes += 1ull << ((feat & 0xfu) * 10);
-        }
-        break;
-      }
-      float thr = __uint_as_float(node.x);
-      idx = (sel12(x, feat) <= thr) ? idx + 1 : (int)(node.y >> 8);
-    }
-  }
-  votes = wave_sum(votes);  // per-field sums stay < 1024: no cross-field carry
-#pragma unroll
-  for (int c = 0; c < C; ++c) acc[c] = wave_sum(acc[c]);
-  if (lane == 0) {
-    float best = -INFINITY;
-    int bi = 0;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      float sc = acc[c] + vote_count(votes, c);
-      if (sc > best) { best = sc; bi = c; }
-    }
-    out[row] = bi;
-  }
+  float sc[C];
+  rf_wave_scores<C>(X, row, lane, nodes, roots, leaf_proba, T, sc);
+  if (lane == 0) out[row] = first_max<C>(sc).idx;
 }
 
 // Below RF_STREAM_MIN_ROWS rows the default stays with the row-per-lane
@@ -576,12 +543,25 @@ __launch_bounds__(256) __global__ void rf_predict_wave_kernel(
 // level, 16 and 48 behind (same profile).
 #define RF_STREAM_REFILL2 32
 
-extern "C" void launch_rf_predict(const float* X, const unsigned* nodes,
-                                  const unsigned* snodes, const int* roots,
-                                  const float* leaf_proba,
-                                  int* out, long long n, int n_nodes,
-                                  int n_leaves, int T, int C,
-                                  hipStream_t stream) {
+// The streaming kernel's LDS-table variants need more dynamic LDS than the
+// default limit: raised once per instantiation (C, rows per lane).
+template <int C, int R>
+static void rf_stream_allow_lds() {
+  static const hipError_t once = hipFuncSetAttribute(
+      reinterpret_cast<const void*>(&rf_predict_stream_kernel<C, true, R>),
+      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  (void)once;
+}
+
+// Returns 0, or nonzero when no kernel exists for C classes (nothing is
+// launched and the output stays unwritten: the caller must turn that into
+// an error).
+extern "C" int launch_rf_predict(const float* X, const unsigned* nodes,
+                                 const unsigned* snodes, const int* roots,
+                                 const float* leaf_proba,
+                                 int* out, long long n, int n_nodes,
+                                 int n_leaves, int T, int C,
+                                 hipStream_t stream) {
   // TCSDN_RF_MODE (read per launch) picks the large-batch kernel:
   //   6  streaming kernel (lanes advance through trees and rows on their
   //      own), node table staged in LDS, 1024-thread blocks, TWO rows per
@@ -615,20 +595,18 @@ extern "C" void launch_rf_predict(const float* X, const unsigned* nodes,
              : n >= RF_STREAM2_MIN_ROWS && snodes_fit2 ? 6
              : n >= RF_STREAM_MIN_ROWS && snodes_fit ? 5 : 2;
   const bool force_stream = mode_env && (mode == 4 || mode == 5 || mode == 6);
+  const uint2* nd = reinterpret_cast<const uint2*>(nodes);
+  const uint2* snd = reinterpret_cast<const uint2*>(snodes);
   if (n <= 131072 && !force_stream) {  // wave-per-row fills the chip at serve batch sizes
     dim3 wgrid((unsigned)((n + 3) / 4));
-#define RFW_CASE(CV)                                                        \
-  case CV:                                                                  \
-    hipLaunchKernelGGL((rf_predict_wave_kernel<CV>), wgrid, dim3(256), 0,   \
-                       stream, X, reinterpret_cast<const uint2*>(nodes),    \
-                       roots, leaf_proba, out, n, T);                       \
-    return;
-    switch (C) {
-      RFW_CASE(2) RFW_CASE(3) RFW_CASE(4) RFW_CASE(5) RFW_CASE(6) RFW_CASE(7)
-      RFW_CASE(8)
-      default: break;
-    }
-#undef RFW_CASE
+    if (dispatch_int<2, 3, 4, 5, 6, 7, 8>(C, [&](auto c) {
+          hipLaunchKernelGGL((rf_predict_wave_kernel<decltype(c)::value>), wgrid,
+                             dim3(256), 0, stream, X, nd, roots, leaf_proba, out,
+                             n, T);
+        }))
+      return 0;
+    // 12 and 16 classes have no wave kernel: the row-per-lane kernel below
+    // takes them at every n
   }
   if (mode >= 4 && mode <= 6 && n > 0 && n_nodes > 0 && n_leaves > 0 && T > 0) {
     // One row range per resident wave: the drain tail, the last rows of a
@@ -658,36 +636,20 @@ extern "C" void launch_rf_predict(const float* X, const unsigned* nodes,
     dim3 sgrid((unsigned)((waves + sb / WAVE - 1) / (sb / WAVE)));
     size_t slds = (two_rows ? 2 * feat_set : (size_t)sb * 13 * sizeof(float)) +
                   (lds_nodes ? snode_bytes : 0);
-#define RFS_LAUNCH(CV, LN, RV)                                               \
-  do {                                                                       \
-    if (LN) {                                                                \
-      static bool once = false;                                              \
-      if (!once) {                                                           \
-        hipFuncSetAttribute(reinterpret_cast<const void*>(                   \
-                                &rf_predict_stream_kernel<CV, LN, RV>),      \
-                            hipFuncAttributeMaxDynamicSharedMemorySize,      \
-                            160 * 1024);                                     \
-        once = true;                                                         \
-      }                                                                      \
-    }                                                                        \
-    hipLaunchKernelGGL((rf_predict_stream_kernel<CV, LN, RV>), sgrid,        \
-                       dim3(sb), slds, stream, X,                            \
-                       reinterpret_cast<const uint2*>(snodes), leaf_proba,   \
-                       out, n, (int)range, n_nodes, n_leaves, T, refill);    \
-  } while (0)
-#define RFS_CASE(CV)                                                         \
-  case CV:                                                                   \
-    if (two_rows) RFS_LAUNCH(CV, true, 2);                                   \
-    else if (lds_nodes) RFS_LAUNCH(CV, true, 1);                             \
-    else RFS_LAUNCH(CV, false, 1);                                           \
-    return;
-    switch (C) {
-      RFS_CASE(2) RFS_CASE(3) RFS_CASE(4) RFS_CASE(5) RFS_CASE(6) RFS_CASE(7)
-      RFS_CASE(8) RFS_CASE(12) RFS_CASE(16)
-      default: break;
-    }
-#undef RFS_CASE
-#undef RFS_LAUNCH
+    return !dispatch_int<2, 3, 4, 5, 6, 7, 8, 12, 16>(C, [&](auto c) {
+      constexpr int CV = decltype(c)::value;
+      auto* kernel = rf_predict_stream_kernel<CV, false, 1>;
+      if (two_rows) {
+        rf_stream_allow_lds<CV, 2>();
+        kernel = rf_predict_stream_kernel<CV, true, 2>;
+      } else if (lds_nodes) {
+        rf_stream_allow_lds<CV, 1>();
+        kernel = rf_predict_stream_kernel<CV, true, 1>;
+      }
+      hipLaunchKernelGGL(kernel, sgrid, dim3(sb), slds, stream, X, snd,
+                         leaf_proba, out, n, (int)range, n_nodes, n_leaves, T,
+                         refill);
+    });
   }
   if (mode < 0 || mode > 2) mode = 2;
   const int block = 512;
@@ -706,240 +668,16 @@ extern "C" void launch_rf_predict(const float* X, const unsigned* nodes,
   size_t lds = (lds_nodes ? node_bytes : 0) + (lds_probs ? prob_bytes : 0) +
                (lds_feat ? feat_bytes : 0);
   dim3 grid(ts_grid(n, block, 4096));
-#define RF_LAUNCH(CV, LN, LP, LF)                                            \
-  hipLaunchKernelGGL((rf_predict_kernel<CV, LN, LP, LF>), grid, dim3(block), \
-                     lds, stream, X, reinterpret_cast<const uint2*>(nodes),  \
-                     roots, leaf_proba, out, n, n_nodes, n_leaves, T)
-#define RF_CASE(CV)                                                          \
-  case CV:                                                                   \
-    if (lds_feat) {                                                          \
-      if (lds_nodes) RF_LAUNCH(CV, true, false, true);                       \
-      else RF_LAUNCH(CV, false, false, true);                                \
-    } else if (lds_nodes && lds_probs) RF_LAUNCH(CV, true, true, false);     \
-    else if (lds_nodes) RF_LAUNCH(CV, true, false, false);                   \
-    else RF_LAUNCH(CV, false, false, false);                                 \
-    return;
-  switch (C) {
-    RF_CASE(2) RF_CASE(3) RF_CASE(4) RF_CASE(5) RF_CASE(6) RF_CASE(7)
-    RF_CASE(8) RF_CASE(12) RF_CASE(16)
-    default: break;
-  }
-#undef RF_CASE
-#undef RF_LAUNCH
-}
-
-// ---------------------------------------------------------------------------
-// SVC RBF + one-vs-one vote (N2).  SV tiles (features, libsvm dual rows,
-// class ids) stream through LDS; each lane keeps C*(C-1) accumulators
-//   acc[c][r] = sum over SVs of class c of dual[r][sv] * exp(-gamma*d2(x,sv))
-// then dec(i<j) = acc[i][j-1] + acc[j][i] + b[pair], majority vote.
-// The per-SV class branch is wave-UNIFORM (the sv index is uniform across
-// the block), so only the matching unrolled branch executes and all
-// accumulator indices stay compile-time.
-// ---------------------------------------------------------------------------
-#define SVC_TILE 128
-
-template <int C>
-__global__ void svc_predict_kernel(const float* __restrict__ X,
-                                   const float* __restrict__ SV,    // [nsv,F]
-                                   const float* __restrict__ dual,  // [C-1,nsv]
-                                   const unsigned char* __restrict__ svclass,
-                                   const float* __restrict__ intercept,
-                                   int* __restrict__ out,
-                                   long long n, int nsv, float gamma) {
-  constexpr int F = 12;
-  constexpr int CR = C - 1;
-  constexpr int NPAIR = C * (C - 1) / 2;
-  __shared__ __attribute__((aligned(16))) float s_sv[SVC_TILE * F];
-  __shared__ float s_dual[CR * SVC_TILE];
-  __shared__ unsigned char s_cls[SVC_TILE];
-  __shared__ float s_b[NPAIR];
-
-  for (int i = threadIdx.x; i < NPAIR; i += blockDim.x) s_b[i] = intercept[i];
-
-  long long stride = (long long)gridDim.x * blockDim.x;
-  // lock-step row tiles so the SV staging loop stays uniform per block
-  for (long long base = (long long)blockIdx.x * blockDim.x; base < n;
-       base += stride) {
-    long long row = base + threadIdx.x;
-    Row12 x;
-    if (row < n) x = load_row12(X, row);
-    // f64 running accumulators + per-tile f32 partials: a single f32 chain
-    // over tens of thousands of SIGNED near-unit dual terms (thousands of
-    // alphas at the C bound in a non-separable fit) loses the O(1) decision
-    // value to rounding (measured: 24% wrong votes at 35K SVs); a 128-term
-    // f32 partial folded into f64 per tile is exact to ~1e-5 at any nsv
-    double acc[C * CR];
-#pragma unroll
-    for (int i = 0; i < C * CR; ++i) acc[i] = 0.0;
-
-    for (int tile = 0; tile < nsv; tile += SVC_TILE) {
-      int cnt = min(SVC_TILE, nsv - tile);
-      __syncthreads();
-      for (int i = threadIdx.x; i < cnt * F; i += blockDim.x)
-        s_sv[i] = SV[(long long)tile * F + i];
-#pragma unroll
-      for (int r = 0; r < CR; ++r)
-        for (int i = threadIdx.x; i < cnt; i += blockDim.x)
-          s_dual[r * SVC_TILE + i] = dual[(long long)r * nsv + tile + i];
-      for (int i = threadIdx.x; i < cnt; i += blockDim.x)
-        s_cls[i] = svclass[tile + i];
-      __syncthreads();
-      if (row < n) {
-        float accT[C * CR];
-#pragma unroll
-        for (int i = 0; i < C * CR; ++i) accT[i] = 0.f;
-        for (int s = 0; s < cnt; ++s) {
-          float d = 0.f;
-#pragma unroll
-          for (int j = 0; j < F; ++j) {
-            float t = x.v[j] - s_sv[s * F + j];
-            d = fmaf(t, t, d);
-          }
-          float kv = __expf(-gamma * d);
-          int c = s_cls[s];  // wave-uniform
-#pragma unroll
-          for (int cc = 0; cc < C; ++cc) {
-            if (c == cc) {
-#pragma unroll
-              for (int r = 0; r < CR; ++r)
-                accT[cc * CR + r] =
-                    fmaf(s_dual[r * SVC_TILE + s], kv, accT[cc * CR + r]);
-            }
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < C * CR; ++i) acc[i] += (double)accT[i];
-      }
-    }
-    if (row >= n) continue;
-    // OVO vote (first max wins ties, libsvm semantics)
-    int votes[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) votes[c] = 0;
-    int p = 0;
-#pragma unroll
-    for (int i = 0; i < C; ++i)
-#pragma unroll
-      for (int j = i + 1; j < C; ++j, ++p) {
-        double dec = acc[i * CR + (j - 1)] + acc[j * CR + i] + (double)s_b[p];
-        if (dec > 0.0) votes[i]++; else votes[j]++;
-      }
-    int best = -1, bi = 0;
-#pragma unroll
-    for (int c = 0; c < C; ++c)
-      if (votes[c] > best) { best = votes[c]; bi = c; }
-    out[row] = bi;
-  }
-}
-
-// Small-batch variant: ONE WAVE PER ROW, SVs split across lanes.  At serve
-// batch sizes (thousands of rows) the row-per-lane kernel leaves most of
-// the chip idle and each lane walks all nsv SVs serially; here n waves fill
-// the 1024 SIMDs and the per-row latency drops ~100x (serve-path profile:
-// profiles/serve_kernel_trace_r01.md).  SV rows stream from global memory —
-// the working set (nsv * 69 B) stays L2-resident and is shared by every
-// wave.  The per-SV class is NOT wave-uniform here, so the OVO accumulator
-// update is an unrolled compile-time switch on the class id.
-template <int C>
-__launch_bounds__(256) __global__ void svc_predict_wave_kernel(
-    const float* __restrict__ X, const float* __restrict__ SV,
-    const float* __restrict__ dual, const unsigned char* __restrict__ svclass,
-    const float* __restrict__ intercept, int* __restrict__ out, long long n,
-    int nsv, float gamma) {
-  constexpr int F = 12;
-  constexpr int CR = C - 1;
-  constexpr int NPAIR = C * (C - 1) / 2;
-  const int lane = threadIdx.x & (WAVE - 1);
-  const long long row = (long long)blockIdx.x * (blockDim.x / WAVE) +
-                        (threadIdx.x >> 6);
-  if (row >= n) return;
-  Row12 x = load_row12(X, row);  // broadcast load, all lanes same row
-  // f64 per-lane accumulators: the 64-way split already conditions the sum,
-  // but signed bounded-alpha duals at large nsv still overwhelm f32 (same
-  // hazard as the tiled kernel — see comment there)
-  double acc[C * CR];
-#pragma unroll
-  for (int i = 0; i < C * CR; ++i) acc[i] = 0.0;
-  for (int s = lane; s < nsv; s += WAVE) {
-    Row12 sv = load_row12(SV, s);
-    float d = 0.f;
-#pragma unroll
-    for (int j = 0; j < F; ++j) {
-      float t = x.v[j] - sv.v[j];
-      d = fmaf(t, t, d);
-    }
-    float kv = __expf(-gamma * d);
-    int c = svclass[s];
-#pragma unroll
-    for (int cc = 0; cc < C; ++cc) {
-      if (c == cc) {
-#pragma unroll
-        for (int r = 0; r < CR; ++r)
-          acc[cc * CR + r] += (double)(dual[(long long)r * nsv + s] * kv);
-      }
-    }
-  }
-  // cross-lane reduction of the C*(C-1) partial sums
-#pragma unroll
-  for (int i = 0; i < C * CR; ++i) acc[i] = wave_sum(acc[i]);
-  if (lane == 0) {
-    int votes[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) votes[c] = 0;
-    int p = 0;
-#pragma unroll
-    for (int i = 0; i < C; ++i)
-#pragma unroll
-      for (int j = i + 1; j < C; ++j, ++p) {
-        double dec = acc[i * CR + (j - 1)] + acc[j * CR + i] + (double)intercept[p];
-        if (dec > 0.0) votes[i]++; else votes[j]++;
-      }
-    int best = -1, bi = 0;
-#pragma unroll
-    for (int c = 0; c < C; ++c)
-      if (votes[c] > best) { best = votes[c]; bi = c; }
-    out[row] = bi;
-    (void)NPAIR;
-  }
-}
-
-extern "C" void launch_svc_predict(const float* X, const float* SV,
-                                   const float* dual,
-                                   const unsigned char* svclass,
-                                   const float* intercept, int* out,
-                                   long long n, int nsv, int C, float gamma,
-                                   hipStream_t stream) {
-  const int block = 256;
-  // crossover re-measured in round 2 after the f64-accumulator fix: at 65K
-  // rows the wave-per-row kernel beats the tiled one (serve 34.5 -> 39.6M
-  // flows/s), so the cutover moved 32768 -> 131072 (same for RF above)
-  if (n <= 131072) {  // wave-per-row fills the chip at serve batch sizes
-    dim3 wgrid((unsigned)((n + 3) / 4));
-#define SVC_WCASE(CV)                                                       \
-  case CV:                                                                  \
-    hipLaunchKernelGGL((svc_predict_wave_kernel<CV>), wgrid, dim3(block),   \
-                       0, stream, X, SV, dual, svclass, intercept, out, n,  \
-                       nsv, gamma);                                         \
-    return;
-    switch (C) {
-      SVC_WCASE(2) SVC_WCASE(3) SVC_WCASE(4) SVC_WCASE(5) SVC_WCASE(6)
-      default: break;
-    }
-#undef SVC_WCASE
-  }
-  dim3 grid(ts_grid(n, block));
-#define SVC_CASE(CV)                                                        \
-  case CV:                                                                  \
-    hipLaunchKernelGGL((svc_predict_kernel<CV>), grid, dim3(block), 0,      \
-                       stream, X, SV, dual, svclass, intercept, out, n,     \
-                       nsv, gamma);                                         \
-    return;
-  switch (C) {
-    SVC_CASE(2) SVC_CASE(3) SVC_CASE(4) SVC_CASE(5) SVC_CASE(6)
-    default: break;
-  }
-#undef SVC_CASE
+  return !dispatch_int<2, 3, 4, 5, 6, 7, 8, 12, 16>(C, [&](auto c) {
+    constexpr int CV = decltype(c)::value;
+    auto* kernel = lds_feat ? (lds_nodes ? rf_predict_kernel<CV, true, false, true>
+                                         : rf_predict_kernel<CV, false, false, true>)
+                   : lds_nodes && lds_probs ? rf_predict_kernel<CV, true, true, false>
+                   : lds_nodes ? rf_predict_kernel<CV, true, false, false>
+                               : rf_predict_kernel<CV, false, false, false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(block), lds, stream, X, nd, roots,
+                       leaf_proba, out, n, n_nodes, n_leaves, T);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1050,22 +788,19 @@ __global__ void knn_topk_kernel(const float* __restrict__ Q,
   }
 }
 
-extern "C" void launch_knn_topk(const float* Q, const float* R,
-                                const unsigned char* ry, float* out_d,
-                                int* out_i, int* out_lab, long long nq,
-                                long long nr, int k, int C, long long idx_base,
-                                hipStream_t stream) {
+// Returns 0, or nonzero when no kernel exists for this k (nothing is
+// launched and the outputs stay unwritten: the caller must turn that into
+// an error).
+extern "C" int launch_knn_topk(const float* Q, const float* R,
+                               const unsigned char* ry, float* out_d,
+                               int* out_i, int* out_lab, long long nq,
+                               long long nr, int k, int C, long long idx_base,
+                               hipStream_t stream) {
   const int block = 256;
   dim3 grid(ts_grid(nq, block));
-#define KNN_CASE(KV)                                                        \
-  case KV:                                                                  \
-    hipLaunchKernelGGL((knn_topk_kernel<KV>), grid, dim3(block), 0, stream, \
-                       Q, R, ry, out_d, out_i, out_lab, nq, nr, C, idx_base); \
-    return;
-  switch (k) {
-    KNN_CASE(1) KNN_CASE(2) KNN_CASE(3) KNN_CASE(4) KNN_CASE(5) KNN_CASE(6)
-    KNN_CASE(7) KNN_CASE(8) KNN_CASE(16) KNN_CASE(32)
-    default: break;
-  }
-#undef KNN_CASE
+  return !dispatch_int<1, 2, 3, 4, 5, 6, 7, 8, 16, 32>(k, [&](auto kv) {
+    hipLaunchKernelGGL((knn_topk_kernel<decltype(kv)::value>), grid,
+                       dim3(block), 0, stream, Q, R, ry, out_d, out_i, out_lab,
+                       nq, nr, C, idx_base);
+  });
 }

@@ -21,27 +21,19 @@
 
 #include "common.h"
 
-// Label and confidence from the C sums.  Only compile-time indices into sc[] (register-pressure rule of
-// predict_kernels.hip).
+// Label and confidence from the C sums.
 template <int C>
 DEV void rf_scores_finish(const float (&sc)[C], float fT, int& label, float& conf) {
-  float best = -INFINITY;
-  int bi = 0;
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    if (sc[c] > best) { best = sc[c]; bi = c; }
-  }
-  label = bi;
-  conf = best / fT;
+  const ArgMax m = first_max<C>(sc);
+  label = m.idx;
+  conf = m.val / fT;
 }
 
 // ---------------------------------------------------------------------------
-// Wave-per-row (serve batch sizes): trees split across the 64 lanes as in
-// rf_predict_wave_kernel, the packed counter and the C partial sums reduced
-// with wave_sum, lane 0 stores.  Per lane the mixed leaves are added in tree
-// order and the reduction tree is wave_sum's, exactly the arithmetic of
-// rf_predict_wave_kernel — so below the cutover the sums, and with them the
-// labels, are those of rf_argmax bit for bit.
+// Wave-per-row (serve batch sizes): the sums come from rf_wave_scores
+// (common.h), the body rf_predict_wave_kernel calls too, and lane 0 stores —
+// so below the cutover the sums, and with them the labels, are those of
+// rf_argmax bit for bit.
 // ---------------------------------------------------------------------------
 template <int C, bool WANT_PROBA>
 __launch_bounds__(256) __global__ void rf_scores_wave_kernel(
@@ -53,38 +45,10 @@ __launch_bounds__(256) __global__ void rf_scores_wave_kernel(
   const long long row = (long long)blockIdx.x * (blockDim.x / WAVE) +
                         (threadIdx.x >> 6);
   if (row >= n) return;  // wave-uniform
-  Row12 x = load_row12(X, row);  // broadcast load
-  float acc[C];
-#pragma unroll
-  for (int c = 0; c < C; ++c) acc[c] = 0.f;
-  unsigned long long votes = 0ull;  // 10-bit packed per-class pure counts
-  for (int t = lane; t < T; t += WAVE) {
-    int idx = roots[t];
-    while (true) {
-      uint2 node = nodes[idx];
-      unsigned feat = node.y & 0xffu;
-      if (feat >= 0xf0u) {
-        if (feat == 0xffu) {
-          int pr = (int)node.x * C;
-#pragma unroll
-          for (int c = 0; c < C; ++c) acc[c] += leaf_proba[pr + c];
-        } else {
-          votes += 1ull << ((feat & 0xfu) * 10);
-        }
-        break;
-      }
-      float thr = __uint_as_float(node.x);
-      idx = (sel12(x, feat) <= thr) ? idx + 1 : (int)(node.y >> 8);
-    }
-  }
-  votes = wave_sum(votes);  // per-field sums stay < 1024: no cross-field carry
-#pragma unroll
-  for (int c = 0; c < C; ++c) acc[c] = wave_sum(acc[c]);
+  float sc[C];
+  rf_wave_scores<C>(X, row, lane, nodes, roots, leaf_proba, T, sc);
   if (lane == 0) {
     const float fT = (float)T;
-    float sc[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) sc[c] = acc[c] + vote_count(votes, c);
     int bi;
     float cf;
     rf_scores_finish<C>(sc, fT, bi, cf);
@@ -192,46 +156,17 @@ extern "C" int launch_rf_scores(const float* X, const unsigned* nodes,
     else if (!strcmp(e, "lane")) wave = false;
   }
   const uint2* nd = reinterpret_cast<const uint2*>(nodes);
-  if (wave) {
-    dim3 wgrid((unsigned)((n + 3) / 4));
-#define RFSW_CASE(CV)                                                        \
-  case CV:                                                                   \
-    if (proba)                                                               \
-      hipLaunchKernelGGL((rf_scores_wave_kernel<CV, true>), wgrid, dim3(256),\
-                         0, stream, X, nd, roots, leaf_proba, proba, labels, \
-                         conf, n, T);                                        \
-    else                                                                     \
-      hipLaunchKernelGGL((rf_scores_wave_kernel<CV, false>), wgrid,          \
-                         dim3(256), 0, stream, X, nd, roots, leaf_proba,     \
-                         proba, labels, conf, n, T);                         \
-    return 0;
-    switch (C) {
-      RFSW_CASE(2) RFSW_CASE(3) RFSW_CASE(4) RFSW_CASE(5) RFSW_CASE(6)
-      RFSW_CASE(7) RFSW_CASE(8)
-    }
-#undef RFSW_CASE
-    return 1;
-  }
-  int cap = 4096;
-  if (const char* e = getenv("TCSDN_RF_PROBA_BLOCKS")) {
-    const int v = atoi(e);
-    if (v >= 1 && v < cap) cap = v;
-  }
-  dim3 grid(ts_grid(n, RF_SCORES_BLOCK, cap));
-#define RFSL_LAUNCH(CV, WP)                                                  \
-  hipLaunchKernelGGL((rf_scores_lane_kernel<CV, WP>), grid,                  \
-                     dim3(RF_SCORES_BLOCK), 0, stream, X, nd, roots,         \
-                     leaf_proba, proba, labels, conf, n, T)
-#define RFSL_CASE(CV)                                                        \
-  case CV:                                                                   \
-    if (proba) RFSL_LAUNCH(CV, true);                                        \
-    else RFSL_LAUNCH(CV, false);                                             \
-    return 0;
-  switch (C) {
-    RFSL_CASE(2) RFSL_CASE(3) RFSL_CASE(4) RFSL_CASE(5) RFSL_CASE(6)
-    RFSL_CASE(7) RFSL_CASE(8)
-  }
-#undef RFSL_CASE
-#undef RFSL_LAUNCH
-  return 1;
+  const dim3 grid = wave ? dim3((unsigned)((n + 3) / 4))
+                         : dim3(ts_grid(n, RF_SCORES_BLOCK,
+                                        env_block_cap("TCSDN_RF_PROBA_BLOCKS", 4096)));
+  const dim3 block(wave ? 256 : RF_SCORES_BLOCK);
+  return !dispatch_int<2, 3, 4, 5, 6, 7, 8>(C, [&](auto c) {
+    constexpr int CV = decltype(c)::value;
+    auto* kernel = wave ? (proba ? rf_scores_wave_kernel<CV, true>
+                                 : rf_scores_wave_kernel<CV, false>)
+                        : (proba ? rf_scores_lane_kernel<CV, true>
+                                 : rf_scores_lane_kernel<CV, false>);
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, X, nd, roots,
+                       leaf_proba, proba, labels, conf, n, T);
+  });
 }

@@ -196,7 +196,7 @@ def svc_predict(
 
 
 # ----------------------------------------------------------------------
-# SVC class probabilities (csrc/svc_proba_kernels.hip)
+# SVC class probabilities (csrc/svc_kernels.hip)
 # ----------------------------------------------------------------------
 
 platt_fit = _cpu.platt_fit  # cold: a fit-time Newton iteration on the host
