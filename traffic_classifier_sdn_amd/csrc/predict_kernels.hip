@@ -316,8 +316,8 @@ __global__ void rf_predict_kernel(const float* __restrict__ X,
 //
 //  * It walks rf_pack's STREAM table (layout there).  A leaf's link is the
 //    next tree's root, so a lane steps from leaf to root with no roots[]
-//    load; a leaf "goes right" because its byte is clamped to slot 12 of the
-//    lane's 13-slot LDS row, which holds NaN.
+//    load; a leaf "goes right" because it reads slot 12 of the lane's
+//    13-slot LDS row, which holds NaN.
 //  * The LDS rows are FEATURE-MAJOR: slot j of thread tid is
 //    s_feat[j * blockDim.x + tid].  Every lane is at a node of its own and
 //    asks for a feature of its own, and in this layout the bank is
@@ -336,13 +336,62 @@ __global__ void rf_predict_kernel(const float* __restrict__ X,
 //    order.  Per-row cost of the test and the refill is thus shared by many
 //    lanes, which matters because the kernel is bound by instruction issue.
 //
+// COMPACT (modes 5 and 6 whenever the launcher's rule admits it): the host
+// format is made for reading by tests and by the L2 walk; the LDS copy is
+// made for the walk alone.  Every block stages the table once, a handful of
+// nodes per thread, and a row visits about 322 nodes, so whatever can be
+// decided per NODE is decided in the staging loop and stored:
+//
+//    word 1 = link << 16 | slot << 12 | byte        word 0, inner = threshold
+//    word 0, leaf = next root << 16 | (row of the distribution + 1, or 0)
+//
+//  * link, next root, idx, resume and park are LDS BYTE ADDRESSES of nodes:
+//    the node read takes idx as it stands, the left child is idx + 8, and
+//    the link is the high half of word 1, which the select can take by
+//    itself (SDWA WORD_1; when the compiler does not fold it, one shift).
+//  * slot << 12 is the byte offset of a feature-major slot in a 1024-thread
+//    block: the feature address is one `and` and one add of the lane's base.
+//  * byte: an inner node has 60; a leaf 0x80 | mixed << 6 | shift.  Every
+//    visit adds 1 << shift to the vote register, where bits 60..63 belong to
+//    no class and may overflow, and t counts byte >= 0x80 by a carry-in: no
+//    branch around the pair.  byte >= 0xc0 is a mixed leaf.
+//  * A flagged leaf links to PARK, so the step is idx = next with no select,
+//    and keeps its real link as the next root in word 0; only
+//    resume = flagged ? (this leaf) : resume remains, and the pass reads the
+//    root back from the leaf (16 bits at resume + 2).  "Flagged" is one
+//    compare of word 1 as a whole: a leaf that links to PARK is the largest
+//    link over the largest slot with a byte of 0x80 or more.  The terminal
+//    entry n_nodes keeps itself as its next root; target >= its address
+//    ends a row.
+//  * The clamps live in the staging loop: a link past the table becomes
+//    PARK, a feature byte above 12 becomes slot 12, a mixed leaf's row is
+//    at most n_leaves - 1, and the two sentinels are written as they must be
+//    whatever the table holds in their place.  The walk has no `min`.  So
+//    for ANY table every idx is the address of one of the n_nodes + 2
+//    entries, every slot one of the lane's 13 and every row one of
+//    leaf_proba's: nothing outside them is read.  (A leaf without a flag
+//    whose link was clamped to PARK counts as flagged and ends its row.)
+//
+// Loop control is one scalar counter (`pending`, at its declaration): a run
+// of steps between two passes is a do-while with one compare and one branch.
+// The steps of the run are what the counter holds beyond the slots that
+// parked, and those are the slots the pass serves: a slot has a live
+// `resume` only from a flagged leaf of this run, because every pass resets
+// it, for the rows that go on as well as for those that end.
+//
 // Termination: in a table rf_pack accepted every link points forward, so a
 // running lane reaches a flagged leaf within n_nodes steps and a pass
 // follows; the wave leaves when its range is used up and every lane is
-// idle.  Some lane runs in every iteration and a row's path is shorter than
-// n_nodes + 2, so a wave needs fewer than rows x (n_nodes + 2) iterations;
-// it gives up at that count, which bounds the loop for any other table
-// too, and no index past the table is ever loaded.
+// idle.  Some lane runs in every step and a row's path is shorter than
+// n_nodes + 2, so a wave needs fewer than rows x (n_nodes + 2) steps.  For
+// any other table `pending` forces a pass after at most slots << kshift
+// steps; every pass takes the steps of the run before it off `budget`,
+// which starts at that product, and the wave gives up when it is spent.
+// No table makes that count come out short: a pass serves at most the
+// slots that added their 1 << kshift in the run (more can have added: a
+// malformed PARK entry, a link clamped onto it), and the difference is
+// taken saturating, at least 1.  So whatever the table holds a wave makes
+// fewer than rows x (n_nodes + 2) + (slots << kshift) steps.
 //
 // Per row the arithmetic is the row-per-lane kernel's: trees in index
 // order, mixed leaves added to acc in that order, the majority test after
@@ -356,12 +405,31 @@ __global__ void rf_predict_kernel(const float* __restrict__ X,
 // (slot s, feature j at s_feat[(s * 13 + j) * blockDim.x + tid]).  An
 // iteration issues the R node reads, then the R feature reads, then does
 // the R updates, so the two LDS latencies of a visit overlap across slots
-// and the loop's scalar work (branches, ballot, budget) is shared by R
+// and the loop's scalar work (branch, ballots, counter) is shared by R
 // visits.  A pass serves slot 0 and then slot 1, the cursor running on from
-// one to the other; `waiting`, `pass_min` and the exit condition count
+// one to the other; `pending`, `pass_min` and the exit condition count
 // slots, R x 64 per wave.  In every iteration some slot advances, so the
 // iteration bound is unchanged.
-template <int C, bool LDS_NODES, int R>
+#define RF_LDS __attribute__((address_space(3)))
+
+// LDS byte address of a pointer into the block's shared memory.
+__device__ __forceinline__ unsigned rf_lds_addr(const void* p) {
+  return (unsigned)(size_t)(RF_LDS const char*)p;
+}
+
+// Load from an LDS byte address held in a register: the address is the
+// ds_read's operand as it stands, with no base to add.
+template <typename T>
+__device__ __forceinline__ T rf_lds_load(unsigned addr) {
+  return *(RF_LDS const T*)(size_t)addr;
+}
+__device__ __forceinline__ uint2 rf_lds_load_node(unsigned addr) {  // one ds_read_b64
+  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+  const u32x2 v = rf_lds_load<u32x2>(addr);
+  return make_uint2(v.x, v.y);
+}
+
+template <int C, bool LDS_NODES, int R, bool COMPACT>
 __launch_bounds__(LDS_NODES ? 1024 : 256)
 __global__ void rf_predict_stream_kernel(const float* __restrict__ X,
                                          const uint2* __restrict__ snodes,
@@ -370,6 +438,7 @@ __global__ void rf_predict_stream_kernel(const float* __restrict__ X,
                                          int rows_per_wave, int n_nodes,
                                          int n_leaves, int T, int pass_min) {
   static_assert(R == 1 || (R == 2 && LDS_NODES), "two rows per lane need the LDS table");
+  static_assert(!COMPACT || LDS_NODES, "the compact form is made while staging into LDS");
   constexpr int BLOCK = LDS_NODES ? 1024 : 256;  // the launcher's block size
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint2* s_nodes = reinterpret_cast<uint2*>(smem);
@@ -379,8 +448,44 @@ __global__ void rf_predict_stream_kernel(const float* __restrict__ X,
 #pragma unroll
   for (int s = 0; s < R; ++s)  // NaN: leaves compare false
     my_feat[(s * 13 + 12) * BLOCK] = __uint_as_float(0x7fc00000u);
+  // What idx, resume and park hold: a node's index, or (COMPACT) its LDS byte
+  // address.  node0 is node 0, `step` the way to the left child, `fin` the
+  // terminal entry n_nodes and `park` the PARK entry.
+  // COMPACT keeps addresses in 16 bits, and the launcher's rule
+  // ((n_nodes + 2) * 8 <= 65536) counts from LDS address 0: this kernel has
+  // no static __shared__ object, so its dynamic segment, and node 0, start
+  // there.  Give it one and that rule has to shrink by its size.
+  const unsigned node0 = COMPACT ? rf_lds_addr(s_nodes) : 0u;
+  constexpr unsigned step = COMPACT ? 8u : 1u;
+  const unsigned fin = node0 + (unsigned)n_nodes * step;
+  const unsigned park = fin + step;
+  // COMPACT: word 1 of a leaf that links to PARK, and of nothing else, is at
+  // least this (PARK's own byte is below 0x80)
+  const unsigned flag_min = park << 16 | 12u << 12 | 0x80u;
   if (LDS_NODES) {
-    for (int i = threadIdx.x; i < n_nodes + 2; i += blockDim.x) s_nodes[i] = snodes[i];
+    for (int i = threadIdx.x; i < n_nodes + 2; i += blockDim.x) {
+      uint2 nd = snodes[i];
+      if (COMPACT) {
+        // Re-encode (COMPACT, above).  Every clamp of the walk is made
+        // here, once per node, so that the walk itself needs none.
+        const unsigned byte = nd.y & 0xffu;
+        const unsigned to = node0 + min(nd.y >> 8, (unsigned)n_nodes + 1u) * 8u;
+        const bool leaf = byte >= 0x80u, flagged = byte >= 0xc0u;
+        unsigned low = 60u;  // inner node: slot 0..12 | shift 60
+        if (leaf) {
+          // the launcher starts this kernel only with 1 <= n_leaves < 65535,
+          // so row1 is at most n_leaves and fits the low half
+          const unsigned row1 = nd.x ? min(nd.x - 1u, (unsigned)(n_leaves - 1)) + 1u : 0u;
+          nd.x = to << 16 | row1;
+          low = 0x80u | (row1 ? 0x40u : 0u) | (byte & 63u);
+        }
+        nd.y = (flagged ? park : to) << 16 | min(byte, 12u) << 12 | low;
+        // the two sentinels are made here, whatever the table holds there
+        if (i == n_nodes) nd = make_uint2(fin << 16, park << 16 | 12u << 12 | 0x80u | 60u);
+        if (i == n_nodes + 1) nd = make_uint2(0u, park << 16 | 12u << 12 | 60u);
+      }
+      s_nodes[i] = nd;
+    }
     __syncthreads();
   }
 
@@ -397,11 +502,19 @@ __global__ void rf_predict_stream_kernel(const float* __restrict__ X,
   if (count <= 0) return;  // wave-uniform
   const float* __restrict__ Xw = X + begin * 12;
   int* __restrict__ outw = out + begin;
-  const unsigned park = (unsigned)n_nodes + 1u;
+  const unsigned feat0 = rf_lds_addr(my_feat);  // COMPACT: this lane's slot 0, row 0
 
   // wave-uniform
   int cursor = 0;  // next unassigned row of the range
-  int waiting = 0, trigger = 0;
+  // One counter ends a run of steps: every slot that parks at a flagged leaf
+  // adds 1 << kshift to it and every step adds 1, and the pass is due at
+  // `due` = (parked slots wanted) << kshift.  1 << kshift exceeds the
+  // n_nodes + 2 steps within which every running slot of a table rf_pack
+  // made has parked, so there the steps never bring a pass forward; with
+  // any other table they force one, which is harmless (a pass serves
+  // whoever waits) and is where `budget` is looked at.
+  const int kshift = min(32 - __clz(n_nodes + 2), 23);
+  unsigned pending = 0, due = 0;
   long long budget = (long long)count * (n_nodes + 2);
   // per slot; every slot starts idle: parked with nothing to resume
   unsigned idx[R], resume[R];
@@ -420,11 +533,13 @@ __global__ void rf_predict_stream_kernel(const float* __restrict__ X,
   }
 
   while (true) {
-    if (waiting >= trigger) {  // PASS: serve the parked slots, slot by slot
-      int nidle_all = 0;
+    {  // PASS: serve the parked slots, slot by slot
+      int nidle_all = 0, served = 0;
 #pragma unroll
       for (int s = 0; s < R; ++s) {
-        if (idx[s] == park && resume[s] != park) {  // waits at a flagged leaf
+        const bool waits = idx[s] == park && resume[s] != park;  // at a flagged leaf
+        served += __popcll(__ballot(waits));
+        if (waits) {
           float m1 = -INFINITY, m2 = -INFINITY;
           int bi = 0;
 #pragma unroll
@@ -436,13 +551,17 @@ __global__ void rf_predict_stream_kernel(const float* __restrict__ X,
             m1 = lead ? sc : m1;
             bi = lead ? c : bi;
           }
+          // where the row goes on: the next tree's root, which the compact
+          // form keeps in the leaf the slot parked on
+          const unsigned target =
+              COMPACT ? rf_lds_load<unsigned short>(resume[s] + 2u) : resume[s];
           // t trees are done, T - t are left; a link to n_nodes ends the row
-          if (resume[s] >= (unsigned)n_nodes || m1 - m2 > (float)(T - t[s])) {
-            outw[row[s]] = bi;
-            resume[s] = park;  // idle
+          if (target >= fin || m1 - m2 > (float)(T - t[s])) {
+            outw[row[s]] = bi;  // idx stays on PARK: idle
           } else {
-            idx[s] = resume[s];
+            idx[s] = target;
           }
+          resume[s] = park;  // live only from a flagged leaf to the pass after it
         }
         const unsigned long long idle = __ballot(idx[s] == park);
         int nidle = __popcll(idle);
@@ -460,7 +579,7 @@ __global__ void rf_predict_stream_kernel(const float* __restrict__ X,
             votes[s] = 0ull;
             row[s] = r;
             t[s] = 0;
-            idx[s] = 0;
+            idx[s] = node0;
           }
           const int take = min(nidle, count - cursor);
           cursor += take;
@@ -469,46 +588,95 @@ __global__ void rf_predict_stream_kernel(const float* __restrict__ X,
         nidle_all += nidle;
       }
       if (nidle_all == R * WAVE) break;  // range used up and every slot idle
+      // The steps of the run before this pass: `pending` less what the
+      // slots served here added.  Only a slot that met a flagged leaf in
+      // that run has a live resume (it is reset below, and the leaf added
+      // 1 << kshift then), so served << kshift never exceeds what was
+      // added; should it ever, the run still costs 1.
+      const unsigned added = (unsigned)served << kshift;
+      budget -= pending > added ? pending - added : 1u;
+      if (budget < 0) break;  // not a table rf_pack made
       // slots still idle stay so; the next pass is due when pass_min slots
       // wait, or all that still run
-      trigger = min(pass_min, R * WAVE - nidle_all);
-      waiting = 0;
+      due = (unsigned)min(pass_min, R * WAVE - nidle_all) << kshift;
+      pending = 0;
     }
-    if (budget == 0) break;  // not a table rf_pack made
-    --budget;
-
-    // one visit per slot: all node reads, then all feature reads, then the
-    // updates, so the slots' LDS latencies overlap
-    uint2 node[R];
-    unsigned byte[R];
-    float fv[R];
+    do {
+      // one visit per slot: all node reads, then all feature reads, then the
+      // updates, so the slots' LDS latencies overlap
+      uint2 node[R];
+      unsigned byte[R];
+      float fv[R];
+      int parked = 0;
 #pragma unroll
-    for (int s = 0; s < R; ++s) node[s] = LDS_NODES ? s_nodes[idx[s]] : snodes[idx[s]];
+      for (int s = 0; s < R; ++s)
+        node[s] = COMPACT ? rf_lds_load_node(idx[s])
+                          : LDS_NODES ? s_nodes[idx[s]] : snodes[idx[s]];
 #pragma unroll
-    for (int s = 0; s < R; ++s) {
-      byte[s] = node[s].y & 0xffu;
-      fv[s] = my_feat[(s * 13 + (int)min(byte[s], 12u)) * BLOCK];
-    }
-#pragma unroll
-    for (int s = 0; s < R; ++s) {
-      unsigned next = (fv[s] <= __uint_as_float(node[s].x)) ? idx[s] + 1u : node[s].y >> 8;
-      next = min(next, park);
-      if (byte[s] >= 0x80u) {  // leaf (some lane is at one nearly every step)
-        votes[s] += 1ull << (byte[s] & 63u);
-        ++t[s];
-        if (node[s].x != 0u) {  // mixed leaf: row + 1 of its distribution
-          const int pr = (int)min(node[s].x - 1u, (unsigned)(n_leaves - 1)) * C;
+      for (int s = 0; s < R; ++s) {
+        byte[s] = node[s].y & 0xffu;
+        fv[s] = COMPACT ? rf_lds_load<float>((node[s].y & 0xf000u) + feat0 +
+                                             (unsigned)(s * 13 * BLOCK * 4))
+                        : my_feat[(s * 13 + (int)min(byte[s], 12u)) * BLOCK];
+      }
+      // COMPACT: a mixed leaf (byte 0xc0 and up) adds the distribution whose
+      // row + 1, clamped while staging, is the low half of word 0
+      auto add_mixed = [&](int s) {
+        if (byte[s] >= 0xc0u) {
+          const int pr = (int)((node[s].x & 0xffffu) - 1u) * C;
 #pragma unroll
           for (int c = 0; c < C; ++c) acc[s][c] += leaf_proba[pr + c];
         }
+      };
+      if (COMPACT && R > 1) {
+        // mixed leaves are rare: one scalar branch skips both slots' masked
+        // regions when no lane is at one (measured: 7 % of mode 6's time).
+        // With one slot the region's own skip is that branch already.
+        bool mixed = false;
+#pragma unroll
+        for (int s = 0; s < R; ++s) mixed |= byte[s] >= 0xc0u;
+        if (__any(mixed)) {
+#pragma unroll
+          for (int s = 0; s < R; ++s) add_mixed(s);
+        }
       }
-      const bool flagged = byte[s] >= 0xc0u;  // leaf of a tree the test follows
-      waiting += __popcll(__ballot(flagged));
-      resume[s] = flagged ? next : resume[s];
-      idx[s] = flagged ? park : next;
-    }
+#pragma unroll
+      for (int s = 0; s < R; ++s) {
+        const bool left = fv[s] <= __uint_as_float(node[s].x);
+        unsigned next = left ? idx[s] + step : node[s].y >> (COMPACT ? 16 : 8);
+        if (!COMPACT) next = min(next, park);
+        if (COMPACT) {
+          // every node counts: an inner node's shift is 60, into the bits of
+          // the vote register that belong to no class
+          votes[s] += 1ull << (byte[s] & 63u);
+          t[s] += byte[s] >= 0x80u;
+          if (R == 1) add_mixed(s);
+        } else if (byte[s] >= 0x80u) {  // leaf (some lane is at one nearly every step)
+          votes[s] += 1ull << (byte[s] & 63u);
+          ++t[s];
+          if (node[s].x != 0u) {  // mixed leaf: row + 1 of its distribution
+            const int pr = (int)min(node[s].x - 1u, (unsigned)(n_leaves - 1)) * C;
+#pragma unroll
+            for (int c = 0; c < C; ++c) acc[s][c] += leaf_proba[pr + c];
+          }
+        }
+        // leaf of a tree the test follows
+        const bool flagged = COMPACT ? node[s].y >= flag_min : byte[s] >= 0xc0u;
+        parked += __popcll(__ballot(flagged));
+        if (COMPACT) {  // a flagged leaf links to PARK: remember the leaf
+          resume[s] = flagged ? idx[s] : resume[s];
+          idx[s] = next;
+        } else {
+          resume[s] = flagged ? next : resume[s];
+          idx[s] = flagged ? park : next;
+        }
+      }
+      pending += ((unsigned)parked << kshift) + 1u;
+    } while (pending < due);
   }
 }
+
+#undef RF_LDS
 
 // Small-batch variant: ONE WAVE PER ROW, trees split across lanes.  At
 // serve batch sizes the row-per-lane kernel runs a ~900-step serial
@@ -534,21 +702,25 @@ __launch_bounds__(256) __global__ void rf_predict_wave_kernel(
 // stages the node table, and a wave wants many rows to refill from.  With
 // two rows per lane a wave wants twice as many, so mode 6 takes over from
 // mode 5 at RF_STREAM2_MIN_ROWS.  Measured on the reference forest, ms per
-// call for modes 2 / 5 / 6 (profiles/rf_predict_stream2.md): 500k rows
-// 0.225 / 0.234 / 0.232, 750k 0.362 / 0.308 / 0.321, 1.5M 0.601 / 0.515 /
-// 0.513, 2M 0.784 / 0.654 / 0.629, 10M 3.79 / 2.89 / 2.55.
-#define RF_STREAM_MIN_ROWS 750000
+// call for modes 2 / 5 / 6 (profiles/rf_predict_compact.md): 140k rows
+// 0.165 / 0.099 / 0.164, 500k 0.216 / 0.167 / 0.170, 1M 0.413 / 0.276 /
+// 0.292, 1.5M 0.600 / 0.376 / 0.382, 2M 0.793 / 0.481 / 0.469, 10M 3.78 /
+// 2.10 / 1.83.  With the compact table mode 5 is ahead of mode 2 at every
+// size measured, down to 140k rows, just above the wave-per-row cutover
+// (131 072 rows and below); nothing was measured between the two, and the
+// 140k value rests on that one point, 0.099 against 0.165 ms.
+#define RF_STREAM_MIN_ROWS 140000
 #define RF_STREAM2_MIN_ROWS 1500000
 // Mode 6's parked slots (of 128 per wave) that start a pass: 24 and 32 are
-// level, 16 and 48 behind (same profile).
+// level, 16 and 48 behind (same profile).  Mode 5 (of 64): 16.
 #define RF_STREAM_REFILL2 32
 
 // The streaming kernel's LDS-table variants need more dynamic LDS than the
 // default limit: raised once per instantiation (C, rows per lane).
-template <int C, int R>
+template <int C, int R, bool COMPACT>
 static void rf_stream_allow_lds() {
   static const hipError_t once = hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&rf_predict_stream_kernel<C, true, R>),
+      reinterpret_cast<const void*>(&rf_predict_stream_kernel<C, true, R, COMPACT>),
       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   (void)once;
 }
@@ -585,7 +757,8 @@ extern "C" int launch_rf_predict(const float* X, const unsigned* nodes,
   // Measured on the 100-tree reference forest, 10M rows: modes 0/1/2 =
   // 2.09/2.12/2.60 Gflows/s (profiles/kernel_opt_r02.md), modes 4/5 against
   // mode 2 in profiles/rf_predict_stream.md, the feature-major rows and
-  // mode 6 in profiles/rf_predict_stream2.md.
+  // mode 6 in profiles/rf_predict_stream2.md, the compact LDS table of
+  // modes 5 and 6 in profiles/rf_predict_compact.md.
   const size_t snode_bytes = (size_t)(n_nodes + 2) * sizeof(uint2);
   const size_t feat_set = 1024 * 13 * sizeof(float);  // one row per thread of a block
   const bool snodes_fit = snode_bytes + feat_set <= 160 * 1024;
@@ -619,7 +792,15 @@ extern "C" int launch_rf_predict(const float* X, const unsigned* nodes,
     // Modes 5 and 6 stage the node table in LDS beside the feature rows
     // (one 1024-thread block per CU); a table too big for two sets of rows
     // runs as mode 5, one too big for that as mode 4.
-    const bool two_rows = mode == 6 && snodes_fit2;
+    // The LDS-table kernels walk the COMPACT node form (comment above the
+    // kernel) when its 16-bit fields hold the table: every node's LDS byte
+    // address, so (n_nodes + 2) * 8 <= 65536, i.e. up to 8190 nodes, and a
+    // mixed leaf's row + 1, so n_leaves + 1 < 65536.  A table that fits two
+    // sets of rows has at most 7166 nodes, so two rows per lane exist in the
+    // compact form only (more leaf rows than that run as mode 5); with one
+    // row per lane a table of 8191 to 13 822 nodes walks the host format.
+    const bool compact = snode_bytes <= 65536 && n_leaves + 1 < 65536;
+    const bool two_rows = mode == 6 && snodes_fit2 && compact;
     const bool lds_nodes = mode != 4 && snodes_fit;
     const int slots = two_rows ? 2 * WAVE : WAVE;  // per wave
     const int sb = lds_nodes ? 1024 : 256;
@@ -638,13 +819,16 @@ extern "C" int launch_rf_predict(const float* X, const unsigned* nodes,
                   (lds_nodes ? snode_bytes : 0);
     return !dispatch_int<2, 3, 4, 5, 6, 7, 8, 12, 16>(C, [&](auto c) {
       constexpr int CV = decltype(c)::value;
-      auto* kernel = rf_predict_stream_kernel<CV, false, 1>;
-      if (two_rows) {
-        rf_stream_allow_lds<CV, 2>();
-        kernel = rf_predict_stream_kernel<CV, true, 2>;
+      auto* kernel = rf_predict_stream_kernel<CV, false, 1, false>;
+      if (two_rows) {  // compact always: the table is at most 7166 nodes
+        rf_stream_allow_lds<CV, 2, true>();
+        kernel = rf_predict_stream_kernel<CV, true, 2, true>;
+      } else if (lds_nodes && compact) {
+        rf_stream_allow_lds<CV, 1, true>();
+        kernel = rf_predict_stream_kernel<CV, true, 1, true>;
       } else if (lds_nodes) {
-        rf_stream_allow_lds<CV, 1>();
-        kernel = rf_predict_stream_kernel<CV, true, 1>;
+        rf_stream_allow_lds<CV, 1, false>();
+        kernel = rf_predict_stream_kernel<CV, true, 1, false>;
       }
       hipLaunchKernelGGL(kernel, sgrid, dim3(sb), slds, stream, X, snd,
                          leaf_proba, out, n, (int)range, n_nodes, n_leaves, T,
