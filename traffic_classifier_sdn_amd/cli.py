@@ -10,6 +10,8 @@ gaussiannb (SUBCOMMANDS at traffic_classifier.py:189; the reference's
 unreachable-`knearest` loader bug, SURVEY.md §2.1, is fixed: `knearest`
 loads the KNeighbors checkpoint).  `ensemble` is new here: a soft vote over
 the class probabilities of several checkpoints (models/ensemble.py).
+`--smooth ALPHA [--switch-margin M]` averages each flow's class probabilities
+across passes, for every model that has them (models/smoothing.py).
 
 Telemetry sources:
   --source subprocess   spawn a monitor command (default: the in-package
@@ -132,6 +134,12 @@ def main(argv: Optional[list] = None) -> int:
                         help="append a Confidence column (top class probability) to the table")
     parser.add_argument("--min-confidence", type=float, default=0.0, metavar="P",
                         help="show flows whose confidence is below P as 'unknown' (implies --confidence)")
+    parser.add_argument("--smooth", type=float, default=None, metavar="ALPHA",
+                        help="average each flow's class probabilities across passes with this "
+                             "weight in (0, 1] on the newest; labels and confidence come from the average")
+    parser.add_argument("--switch-margin", type=float, default=0.0, metavar="M",
+                        help="with --smooth: a flow changes its label only when another class "
+                             "leads the average by more than M")
     parser.add_argument("--members", default=DEFAULT_MEMBERS, metavar="A,B,...",
                         help="ensemble: the subcommand names of the member models")
     parser.add_argument("--weights", default=None, metavar="W,W,...",
@@ -182,10 +190,19 @@ def main(argv: Optional[list] = None) -> int:
         print(f"ERROR: {args.subcommand} has no class probabilities: no --confidence",
               file=sys.stderr)
         return 2
+    if args.smooth is not None and not hasattr(model, "predict_proba"):
+        print(f"ERROR: {args.subcommand} has no class probabilities: no --smooth",
+              file=sys.stderr)
+        return 2
     # the streams as they are now, not as they were when serve was imported
-    rc = RealtimeClassifier(model, out=sys.stdout, stats=args.stats, stats_out=sys.stderr,
-                            prometheus_port=args.prometheus,
-                            confidence=confidence, min_confidence=args.min_confidence)
+    try:
+        rc = RealtimeClassifier(model, out=sys.stdout, stats=args.stats, stats_out=sys.stderr,
+                                prometheus_port=args.prometheus,
+                                confidence=confidence, min_confidence=args.min_confidence,
+                                smooth=args.smooth, switch_margin=args.switch_margin)
+    except ValueError as e:  # --smooth or --switch-margin out of range
+        print(f"ERROR: {e}", file=sys.stderr)
+        return 2
     try:
         rc.run(_line_source(args))
     except KeyboardInterrupt:

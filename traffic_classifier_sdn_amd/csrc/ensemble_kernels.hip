@@ -5,6 +5,8 @@
 //   linear_proba_kernel    softmax of the logistic logits
 //   knn_vote_proba_kernel  neighbour vote fractions from a top-k index list
 //   ensemble_vote_kernel   weighted average of up to 8 members' probabilities
+//   proba_smooth_kernel    per-flow moving average of a probability row
+//                          across polls, with a margin for switching labels
 //
 // Conventions of predict_kernels.hip: 12 features and load_row12, parameters
 // broadcast through LDS, grid-stride loops, per-lane arrays sized by a
@@ -281,6 +283,74 @@ __launch_bounds__(PROBA_BLOCK) __global__ void ensemble_vote_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Per-flow smoothing of a probability row across polls.  `state` [cap, C] and
+// `held` [cap] belong to the flow slots; per row r < n, with a and b = 1 - a
+// formed by the caller in f32:
+//   r >= *n_live     state[r] = 0, held[r] = -1; label and conf are the
+//                    first-maximum argmax of proba[r] and that maximum
+//   held[r] < 0      s = proba[r], bit for bit (first sighting)
+//   otherwise        s[c] = fmaf(a, proba[r,c], b * state[r,c]), the product
+//                    rounded once and the fused add once
+// then top = first-maximum argmax of s, and the held label stays unless
+// s[top] - s[held] > margin (an exact tie keeps it, also against a lower
+// class index).  state[r] = s, held[r] = labels[r] = label, conf[r] =
+// s[label]: the smoothed probability of the REPORTED class.
+//
+// The held class is a runtime index: s[held] is a select over the C
+// registers (as ens_add applies its fmaf), which yields -inf for a value
+// outside 0..C-1, so such a row switches to top and nothing is read out of
+// bounds.  n_live is read from memory once per lane, so a captured graph
+// over all cap rows follows a live count that the host changes between
+// replays; null means all n rows are live.  One lane owns a row's state and
+// held entry: no other lane reads or writes them.
+//
+// Traffic per row: 8 C + 4 bytes in (proba, state, held), 4 C + 12 bytes out
+// (state, held, label, conf); a first sighting skips the state read.
+// ---------------------------------------------------------------------------
+template <int C>
+__launch_bounds__(PROBA_BLOCK) __global__ void proba_smooth_kernel(
+    const float* __restrict__ proba, float* __restrict__ state,
+    int* __restrict__ held, const int* __restrict__ n_live, float a, float b,
+    float margin, int* __restrict__ labels, float* __restrict__ conf,
+    long long n) {
+  const long long live = n_live ? (long long)*n_live : n;
+
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x; row < n;
+       row += stride) {
+    float s[C];
+    load_probs<C>(proba, row, s);
+    if (row >= live) {
+      const ArgMax m = first_max<C>(s);
+      labels[row] = m.idx;
+      conf[row] = m.val;
+#pragma unroll
+      for (int c = 0; c < C; ++c) s[c] = 0.f;
+      store_probs<C>(state, row, s);
+      held[row] = -1;
+      continue;
+    }
+    const int h = held[row];
+    if (h >= 0) {
+      float old[C];
+      load_probs<C>(state, row, old);
+#pragma unroll
+      for (int c = 0; c < C; ++c) s[c] = fmaf(a, s[c], __fmul_rn(b, old[c]));
+    }
+    const ArgMax m = first_max<C>(s);
+    float sh = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < C; ++c) sh = h == c ? s[c] : sh;
+    const bool keep = h >= 0 && !(m.val - sh > margin);
+    const int label = keep ? h : m.idx;
+    store_probs<C>(state, row, s);
+    held[row] = label;
+    labels[row] = label;
+    conf[row] = keep ? sh : m.val;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Launchers.  Each returns 0, or nonzero when a class or member count is out
 // of range (nothing is launched and the outputs stay unwritten: the caller
 // must turn that into an error).
@@ -346,5 +416,23 @@ extern "C" int launch_ensemble_vote(const EnsembleArgs* args, float* avg,
     auto* kernel = avg ? ensemble_vote_kernel<CV, true> : ensemble_vote_kernel<CV, false>;
     hipLaunchKernelGGL(kernel, grid, dim3(PROBA_BLOCK), 0, stream, *args, avg,
                        labels, conf, n);
+  });
+}
+
+// `n_live` may be null: then all n rows are live.  `state` and `held` have
+// at least n rows; `a` is in (0, 1] and `margin` finite and >= 0.
+extern "C" int launch_proba_smooth(const float* proba, float* state, int* held,
+                                   const int* n_live, float a, float margin,
+                                   int* labels, float* conf, long long n, int C,
+                                   hipStream_t stream) {
+  if (C < 2 || C > 8) return 1;
+  if (!(a > 0.f && a <= 1.f) || !(margin >= 0.f) || margin == INFINITY) return 1;
+  if (n <= 0) return 0;
+  const float b = 1.0f - a;
+  dim3 grid(proba_grid(n));
+  return proba_dispatch(C, [&](auto c) {
+    hipLaunchKernelGGL((proba_smooth_kernel<decltype(c)::value>), grid,
+                       dim3(PROBA_BLOCK), 0, stream, proba, state, held, n_live,
+                       a, b, margin, labels, conf, n);
   });
 }

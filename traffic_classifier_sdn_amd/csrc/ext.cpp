@@ -42,6 +42,8 @@ int launch_knn_vote_proba(const int*, const unsigned char*, float*, long long,
                           int, long long, int, hipStream_t);
 int launch_ensemble_vote(const EnsembleArgs*, float*, int*, float*, long long,
                          int, hipStream_t);
+int launch_proba_smooth(const float*, float*, int*, const int*, float, float,
+                        int*, float*, long long, int, hipStream_t);
 int launch_svc_predict(const float*, const float*, const float*,
                        const unsigned char*, const float*, int*, long long,
                        int, int, float, hipStream_t);
@@ -313,6 +315,54 @@ static std::vector<torch::Tensor> ensemble_vote(
       labels.data_ptr<int>(), conf.data_ptr<float>(), n, (int)C, cur_stream());
   TORCH_CHECK(rc == 0, "ensemble_vote: arguments out of the kernel's range");
   return {avg, labels, conf};
+}
+
+// Returns (labels [n] i32, conf [n] f32); `state` [cap,C] and `held` [cap]
+// are updated in place, rows < n only.  `n_live` is an int32 [1] tensor or
+// None (all n rows are live).
+static std::vector<torch::Tensor> proba_smooth(
+    torch::Tensor proba, torch::Tensor state, torch::Tensor held,
+    c10::optional<torch::Tensor> n_live, double alpha, double margin) {
+  CHECK_IN(proba, torch::kFloat32);
+  CHECK_IN(state, torch::kFloat32);
+  CHECK_IN(held, torch::kInt32);
+  TORCH_CHECK(proba.dim() == 2 && state.dim() == 2 && held.dim() == 1,
+              "proba_smooth takes proba (n,C), state (cap,C) and held (cap)");
+  const long long n = proba.size(0);
+  const int64_t C = proba.size(1);
+  TORCH_CHECK(C >= 2 && C <= 8, "proba_smooth supports 2..8 classes, got ", C);
+  TORCH_CHECK(state.size(1) == C, "state has ", state.size(1), " columns for ", C, " classes");
+  TORCH_CHECK(state.size(0) >= n && held.size(0) >= n,
+              "state and held need at least ", n, " rows");
+  TORCH_CHECK(proba.get_device() == state.get_device() &&
+                  proba.get_device() == held.get_device(),
+              "proba, state and held must be on one device");
+  const char* p0 = static_cast<const char*>(proba.data_ptr());
+  const char* s0 = static_cast<const char*>(state.data_ptr());
+  TORCH_CHECK(p0 + proba.nbytes() <= s0 || s0 + state.nbytes() <= p0,
+              "proba must not alias state");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(p0) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(s0) % 16 == 0,
+              "proba and state must be 16-byte aligned");
+  const int* live = nullptr;
+  if (n_live.has_value()) {
+    const torch::Tensor& n_live_t = n_live.value();
+    CHECK_IN(n_live_t, torch::kInt32);
+    TORCH_CHECK(n_live_t.numel() == 1 && n_live_t.get_device() == proba.get_device(),
+                "n_live must be an int32 [1] tensor on proba's device");
+    live = n_live_t.data_ptr<int>();
+  }
+  const float a = (float)alpha, m = (float)margin;
+  TORCH_CHECK(a > 0.f && a <= 1.f, "alpha must be in (0, 1]");
+  TORCH_CHECK(std::isfinite(m) && m >= 0.f, "margin must be finite and >= 0");
+  auto labels = torch::empty({n}, proba.options().dtype(torch::kInt32));
+  auto conf = torch::empty({n}, proba.options());
+  const int rc = launch_proba_smooth(
+      proba.data_ptr<float>(), state.data_ptr<float>(), held.data_ptr<int>(),
+      live, a, m, labels.data_ptr<int>(), conf.data_ptr<float>(), n, (int)C,
+      cur_stream());
+  TORCH_CHECK(rc == 0, "proba_smooth: arguments out of the kernel's range");
+  return {labels, conf};
 }
 
 static torch::Tensor svc_predict(torch::Tensor X, torch::Tensor SV,
@@ -742,6 +792,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("knn_vote_proba", &knn_vote_proba, "neighbour vote fractions from top-k indices");
   m.def("ensemble_vote", &ensemble_vote,
         "soft vote over member probabilities: (avg | empty, labels, conf)");
+  m.def("proba_smooth", &proba_smooth,
+        "per-flow moving average of a probability row: (labels, conf)",
+        py::arg("proba"), py::arg("state"), py::arg("held"), py::arg("n_live"),
+        py::arg("alpha"), py::arg("margin"));
   m.def("svc_predict", &svc_predict, "RBF Gram + OVO vote");
   m.def("svc_decision", &svc_decision, "RBF Gram + OVO decision values (f64)");
   m.def("svc_couple", &svc_couple,

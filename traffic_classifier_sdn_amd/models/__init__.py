@@ -9,6 +9,7 @@ from .kmeans import KMeans
 from .kneighbors import KNeighborsClassifier
 from .logistic import LogisticRegression
 from .random_forest import RandomForestClassifier
+from .smoothing import FlowSmoother
 from .svc import SVC, CalibratedSVC
 
 _KIND_TO_CLASS = {
@@ -56,6 +57,7 @@ def load_model(path: str, device: Optional[str] = None) -> Estimator:
 __all__ = [
     "CalibratedSVC",
     "Estimator",
+    "FlowSmoother",
     "GaussianNB",
     "KMeans",
     "KNeighborsClassifier",

@@ -621,6 +621,105 @@ def ensemble_vote(
     return (avg if want_proba else None), label.to(torch.int32), conf
 
 
+def proba_smooth_check(proba, state, held, alpha, margin, n_live):
+    """Argument rules of proba_smooth, shared by the CPU and GPU bindings.
+    Returns (a, b, margin) as Python floats holding the f32 values the op
+    works with: a = f32(alpha), b = 1 - a in f32, f32(margin)."""
+    if proba.dim() != 2 or not 2 <= proba.shape[1] <= 8:
+        raise ValueError(f"proba_smooth takes (n, 2..8) probabilities, got {tuple(proba.shape)}")
+    n, C = proba.shape
+    if state.dim() != 2 or state.shape[1] != C or held.dim() != 1:
+        raise ValueError(
+            f"proba_smooth takes state (cap, {C}) and held (cap), got "
+            f"{tuple(state.shape)} and {tuple(held.shape)}"
+        )
+    if state.shape[0] < n or held.shape[0] < n:
+        raise ValueError(
+            f"{n} rows do not fit a state of {state.shape[0]} and a held of {held.shape[0]} rows"
+        )
+    if proba.dtype != torch.float32 or state.dtype != torch.float32 or held.dtype != torch.int32:
+        raise ValueError("proba_smooth takes f32 proba, f32 state and int32 held")
+    if not (proba.is_contiguous() and state.is_contiguous() and held.is_contiguous()):
+        raise ValueError("proba, state and held must be contiguous")
+    if state.device != proba.device or held.device != proba.device:
+        raise ValueError("proba, state and held must be on one device")
+    p0, s0 = proba.data_ptr(), state.data_ptr()
+    if proba.numel() and p0 < s0 + state.numel() * 4 and s0 < p0 + proba.numel() * 4:
+        raise ValueError("proba must not alias state")
+    if n_live is not None:
+        if (
+            not isinstance(n_live, torch.Tensor)
+            or n_live.dtype != torch.int32
+            or tuple(n_live.shape) != (1,)
+            or n_live.device != proba.device
+        ):
+            raise ValueError("n_live must be None or an int32 [1] tensor on proba's device")
+    a = np.float32(alpha)
+    if not (np.float32(0.0) < a <= np.float32(1.0)) or not 0.0 < float(alpha) <= 1.0:
+        raise ValueError(f"alpha must be in (0, 1], got {alpha}")
+    m = np.float32(margin)
+    if not bool(np.isfinite(m)) or not m >= 0 or not np.isfinite(float(margin)):
+        raise ValueError(f"margin must be finite and >= 0, got {margin}")
+    return float(a), float(np.float32(1.0) - a), float(m)
+
+
+def proba_smooth(
+    proba: torch.Tensor,
+    state: torch.Tensor,
+    held: torch.Tensor,
+    alpha: float,
+    margin: float = 0.0,
+    n_live: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-flow smoothing across polls: (label[n] int32, conf[n] f32).
+
+    ``state`` [cap, C] f32 and ``held`` [cap] int32 (-1: never seen) belong
+    to the flow slots and are updated in place, rows < n only.  With a =
+    f32(alpha) and b = 1 - a in f32, per row r:
+
+    * r >= n_live[0]: state[r] = 0, held[r] = -1; label is the
+      first-maximum argmax of proba[r] and conf that maximum;
+    * held[r] < 0: s = proba[r] bit for bit;
+    * otherwise s[c] = fma(a, proba[r,c], b * state[r,c]), the product
+      rounded to f32 once and the fused add once;
+
+    then top = first-maximum argmax of s, and label = held[r] unless
+    s[top] - s[held[r]] > margin (an exact tie keeps the held label).
+    state[r] = s, held[r] = label, conf = s[label].
+
+    The fused step is formed in f64, where a * proba is exact, and rounded
+    to f32: the kernel's fmaf up to the double rounding of the sum.  Nothing
+    here reads a value back to the host, so the same formulation runs on
+    device tensors.
+    """
+    a, b, m = proba_smooth_check(proba, state, held, alpha, margin, n_live)
+    n = proba.shape[0]
+    dev = proba.device
+    if n == 0:
+        return (torch.empty(0, dtype=torch.int32, device=dev),
+                torch.empty(0, dtype=torch.float32, device=dev))
+    old = state[:n]
+    h = held[:n].long()
+    if n_live is None:
+        live = torch.ones(n, dtype=torch.bool, device=dev)
+    else:
+        live = torch.arange(n, device=dev) < n_live.long()
+    seen = live & (h >= 0)
+    ema = (a * proba.double() + (b * old).double()).to(torch.float32)
+    s = torch.where(seen.unsqueeze(1), ema, proba)
+    best = s.max(dim=1).values
+    # the first column that reaches the maximum (see ensemble_vote)
+    top = torch.argmax((s == best.unsqueeze(1)).to(torch.uint8), dim=1)
+    hc = h.clamp(min=0)
+    sh = s.gather(1, hc.unsqueeze(1)).squeeze(1)
+    keep = seen & ~((best - sh) > m)
+    label = torch.where(keep, hc, top)
+    conf = s.gather(1, label.unsqueeze(1)).squeeze(1)
+    state[:n] = torch.where(live.unsqueeze(1), s, torch.zeros_like(s))
+    held[:n] = torch.where(live, label, torch.full_like(label, -1)).to(torch.int32)
+    return label.to(torch.int32), conf
+
+
 # ----------------------------------------------------------------------
 # Serve-path feature extraction (CPU oracle of the GPU kernel; mirrors the
 # reference Flow update math, traffic_classifier.py:63-96)

@@ -467,6 +467,24 @@ def ensemble_vote(
     return (avg if want_proba else None), labels, conf
 
 
+proba_smooth_check = _cpu.proba_smooth_check
+
+
+def proba_smooth(
+    proba: torch.Tensor,
+    state: torch.Tensor,
+    held: torch.Tensor,
+    alpha: float,
+    margin: float = 0.0,
+    n_live: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    # no cast and no copy here: state and held are updated in place, so a
+    # wrong dtype or layout is an error, not something to convert
+    a, _, m = _cpu.proba_smooth_check(proba, state, held, alpha, margin, n_live)
+    labels, conf = _ext.proba_smooth(proba, state, held, n_live, a, m)
+    return labels, conf
+
+
 # ----------------------------------------------------------------------
 # fit ops
 # ----------------------------------------------------------------------

@@ -16,7 +16,7 @@ from __future__ import annotations
 import json
 import sys
 import time
-from typing import Iterable, TextIO
+from typing import Iterable, Optional, TextIO
 
 import numpy as np
 
@@ -69,8 +69,24 @@ class RealtimeClassifier:
         prometheus_port: int = 0,
         confidence: bool = False,
         min_confidence: float = 0.0,
+        smooth: Optional[float] = None,
+        switch_margin: float = 0.0,
     ) -> None:
         self.model = model
+        # smooth=alpha: labels and confidence come from the flow's class
+        # probabilities averaged across passes (models/smoothing.py)
+        self.smoother = None
+        if smooth is not None:
+            from .models.smoothing import FlowSmoother
+
+            if not hasattr(model, "predict_proba") or getattr(model, "classes_", None) is None:
+                raise ValueError(
+                    f"{type(model).__name__} has no class probabilities to smooth"
+                )
+            self.smoother = FlowSmoother(
+                len(model.classes_), 64, smooth, switch_margin,
+                device=getattr(model, "device", "cpu"),
+            )
         # per-flow confidence column; a flow below min_confidence (which
         # implies the column) is shown as "unknown"
         self.min_confidence = float(min_confidence)
@@ -95,6 +111,8 @@ class RealtimeClassifier:
                 self.last_confidence = np.zeros(0, dtype=np.float32)
             return np.asarray([], dtype=object)
         X = table.feature_matrix(dtype=np.float32)
+        if self.smoother is not None:
+            return self._classify_smoothed(X)
         if self.confidence:
             pred, conf = self.model.predict_with_confidence(X)
             self.last_confidence = conf
@@ -111,6 +129,22 @@ class RealtimeClassifier:
                 pred = np.asarray(names, dtype=object)[idx]
             else:
                 pred = map_cluster_labels(pred)
+        return pred
+
+    def _classify_smoothed(self, X: np.ndarray) -> np.ndarray:
+        """Row i of the table is flow slot i of the smoother, for life."""
+        import torch
+
+        sm = self.smoother
+        proba_fn = getattr(self.model, "predict_proba_device", None) or self.model.predict_proba
+        proba = torch.as_tensor(proba_fn(X)).to(device=sm.device, dtype=torch.float32).contiguous()
+        sm.ensure_capacity(proba.shape[0])
+        idx, conf = sm.update(proba)
+        pred = np.asarray(self.model.classes_, dtype=object)[idx.cpu().numpy()]
+        conf = conf.cpu().numpy()
+        if self.confidence:
+            self.last_confidence = conf
+            pred[conf < self.min_confidence] = "unknown"
         return pred
 
     def feed(self, line) -> bool:

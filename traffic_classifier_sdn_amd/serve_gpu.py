@@ -15,6 +15,15 @@ capacity fall back to a plain (non-graph) launch path.
 ``engine.ensemble.classes_``) and ``engine.confidence`` its averaged top
 probability.  The members' probability kernels and the vote kernel are part
 of the same captured graph.
+
+``smooth=alpha`` (with ``ensemble=``) carries each flow's averaged
+probability row from poll to poll (models/smoothing.py): the result gains
+the key ``"smoothed"``, a label that changes only when another class leads
+the moving average by more than ``switch_margin``, and ``engine.confidence``
+the smoothed probability of that label.  ``"ensemble"`` stays the raw vote.
+The smoothing kernel is part of the captured graph too; the live-row count
+reaches it through device memory, so that the rows past it, which the graph
+also runs over, are reset and not averaged.
 """
 
 from __future__ import annotations
@@ -39,6 +48,8 @@ class GpuServeEngine:
         confidence: bool = False,
         ensemble: Optional[Sequence[str]] = None,
         ensemble_weights: Optional[Sequence[float]] = None,
+        smooth: Optional[float] = None,
+        switch_margin: float = 0.0,
     ) -> None:
         self.models = models
         self.capacity = capacity
@@ -86,8 +97,31 @@ class GpuServeEngine:
                     )
             self.ensemble = SoftVoteEnsemble({n: models[n] for n in names}, ensemble_weights)
             self._ens_members = names
-        # every key of self.confidence, in order
-        self._conf_keys = self._conf_models + (["ensemble"] if self.ensemble else [])
+        # per-flow smoothing of the vote's averaged row across polls
+        self.smoother = None
+        if smooth is not None:
+            from .models.smoothing import FlowSmoother
+
+            if self.ensemble is None:
+                raise ValueError("smooth= smooths the vote's probabilities: it needs ensemble=")
+            if "smoothed" in models:
+                raise ValueError("with smooth=, no model can be named 'smoothed'")
+            self.smoother = FlowSmoother(
+                len(self.ensemble.classes_), capacity, smooth, switch_margin, device=self.device
+            )
+            # the live-row count, staged like the counters: the captured
+            # pass runs over all `capacity` rows and reads it on the device
+            self.h_nlive = torch.zeros(1, dtype=torch.int32, pin_memory=pin)
+            self._h_nlive_np = self.h_nlive.numpy()  # same memory, cheap to set
+            self.d_nlive = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self._smooth_table: Optional[FlowTable] = None
+            self._smooth_n = 0
+        # the keys the vote adds to the result, and every key of
+        # self.confidence, in order
+        self._vote_keys = (["ensemble"] if self.ensemble else []) + (
+            ["smoothed"] if self.smoother else []
+        )
+        self._conf_keys = self._conf_models + self._vote_keys
         self.confidence: Dict[str, np.ndarray] = {}
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self.last_latency_s = 0.0
@@ -97,7 +131,8 @@ class GpuServeEngine:
         from . import ops
 
         X = ops.flow_features(self.d_cur, self.d_prev, self.d_times)
-        for name, labels, conf in self._predict_all(X):
+        n_live = self.d_nlive if self.smoother is not None else None
+        for name, labels, conf in self._predict_all(X, n_live):
             if conf is not None:
                 self._keep(self.d_conf, self.h_conf, name, conf)
             self._keep(self.d_labels, self.h_labels, name, labels)
@@ -113,8 +148,9 @@ class GpuServeEngine:
                 value, device="cpu", pin_memory=self.device.type == "cuda"
             )
 
-    def _predict_all(self, X: torch.Tensor):
-        """Yields (name, labels, conf | None) per model, then the vote's.
+    def _predict_all(self, X: torch.Tensor, n_live: Optional[torch.Tensor] = None):
+        """Yields (name, labels, conf | None) per model, then the vote's and,
+        with smooth=, the smoothed verdict's (``n_live``: the smoother's).
         A member's probabilities come from its own kernel next to its
         unchanged label kernel, except the forest's: a forest is walked once
         per poll, by the scores kernel, which gives its probabilities, and
@@ -136,10 +172,19 @@ class GpuServeEngine:
                     probas[name] = model.predict_proba_device(X)
             yield name, labels, conf
         if self.ensemble is not None:
-            _, labels, conf = self.ensemble.vote([probas[n] for n in self._ens_members])
+            avg, labels, conf = self.ensemble.vote(
+                [probas[n] for n in self._ens_members], want_proba=self.smoother is not None
+            )
             yield "ensemble", labels, conf
+            if self.smoother is not None:
+                labels, conf = self.smoother.update(avg, n_live)
+                yield "smoothed", labels, conf
 
     def _capture(self) -> None:
+        # the warm-up passes would each move the smoother on: put its state
+        # back afterwards, so that the first replay is the first update
+        if self.smoother is not None:
+            saved = self.smoother.state.clone(), self.smoother.held.clone()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -150,7 +195,17 @@ class GpuServeEngine:
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             self._compute()
+        if self.smoother is not None:
+            self.smoother.state.copy_(saved[0])
+            self.smoother.held.copy_(saved[1])
         self._graph = g
+
+    def _smooth_begin(self, table: FlowTable, n: int) -> None:
+        """Before a pass over ``table``: a table that shrank or a different
+        table holds other flows in the same slots, so the history goes."""
+        if table is not self._smooth_table or n < self._smooth_n:
+            self.smoother.reset()
+        self._smooth_table, self._smooth_n = table, n
 
     # -- per-poll entry -------------------------------------------------
     def classify(self, table: FlowTable) -> Dict[str, np.ndarray]:
@@ -158,11 +213,17 @@ class GpuServeEngine:
         {model_name: labels[n] int32} (class indices).  With
         ``confidence=True`` the pass also leaves {model_name: float32[n]} in
         ``self.confidence`` for the models that support it.  With
-        ``ensemble=`` both carry the vote's under the key "ensemble"."""
+        ``ensemble=`` both carry the vote's under the key "ensemble", and
+        with ``smooth=`` the smoothed verdict's under "smoothed"."""
         n = len(table)
         t0 = time.perf_counter()
+        if self.smoother is not None:
+            self._smooth_begin(table, n)
         if n > self.capacity:
             return self._classify_unbounded(table)
+        if self.smoother is not None:
+            self._h_nlive_np[0] = n
+            self.d_nlive.copy_(self.h_nlive, non_blocking=True)
         cur, prev, times = table.counters_snapshot()
         self.h_cur[:n] = torch.from_numpy(cur)
         self.h_prev[:n] = torch.from_numpy(prev)
@@ -178,7 +239,7 @@ class GpuServeEngine:
             else:
                 self._compute()
             out = {}
-            keys = list(self.models) + (["ensemble"] if self.ensemble else [])
+            keys = list(self.models) + self._vote_keys
             for name in keys:
                 self.h_labels[name].copy_(self.d_labels[name], non_blocking=True)
             for name in self._conf_keys:
@@ -205,6 +266,8 @@ class GpuServeEngine:
         from . import ops
 
         t0 = time.perf_counter()
+        if self.smoother is not None and self.smoother.ensure_capacity(len(table)):
+            self._graph = None  # it holds the buffers that were just replaced
         cur, prev, times = table.counters_snapshot()
         to = lambda a: torch.from_numpy(a).to(self.device)
         X = ops.flow_features(to(cur), to(prev), to(times))
