@@ -31,6 +31,7 @@ setup(
                 os.path.join(CSRC, "predict_kernels.hip"),
                 os.path.join(CSRC, "rf_proba_kernels.hip"),
                 os.path.join(CSRC, "ensemble_kernels.hip"),
+                os.path.join(CSRC, "traffic_kernels.hip"),
                 os.path.join(CSRC, "svc_kernels.hip"),
                 os.path.join(CSRC, "knn_mfma.hip"),
                 os.path.join(CSRC, "fit_kernels.hip"),

@@ -12,6 +12,8 @@ loads the KNeighbors checkpoint).  `ensemble` is new here: a soft vote over
 the class probabilities of several checkpoints (models/ensemble.py).
 `--smooth ALPHA [--switch-margin M]` averages each flow's class probabilities
 across passes, for every model that has them (models/smoothing.py).
+`--summary` adds a per-class table of flows, packets/s and bytes/s below
+each flow table (ops.class_traffic).
 
 Telemetry sources:
   --source subprocess   spawn a monitor command (default: the in-package
@@ -140,6 +142,10 @@ def main(argv: Optional[list] = None) -> int:
     parser.add_argument("--switch-margin", type=float, default=0.0, metavar="M",
                         help="with --smooth: a flow changes its label only when another class "
                              "leads the average by more than M")
+    parser.add_argument("--summary", action="store_true",
+                        help="below each flow table, print flows, packets/s and bytes/s per "
+                             "traffic class (summed on the model's device); adds them to --stats "
+                             "and --prometheus")
     parser.add_argument("--members", default=DEFAULT_MEMBERS, metavar="A,B,...",
                         help="ensemble: the subcommand names of the member models")
     parser.add_argument("--weights", default=None, metavar="W,W,...",
@@ -199,8 +205,9 @@ def main(argv: Optional[list] = None) -> int:
         rc = RealtimeClassifier(model, out=sys.stdout, stats=args.stats, stats_out=sys.stderr,
                                 prometheus_port=args.prometheus,
                                 confidence=confidence, min_confidence=args.min_confidence,
-                                smooth=args.smooth, switch_margin=args.switch_margin)
-    except ValueError as e:  # --smooth or --switch-margin out of range
+                                smooth=args.smooth, switch_margin=args.switch_margin,
+                                summary=args.summary)
+    except ValueError as e:  # --smooth or --switch-margin out of range, --summary over 8 classes
         print(f"ERROR: {e}", file=sys.stderr)
         return 2
     try:

@@ -44,6 +44,10 @@ int launch_ensemble_vote(const EnsembleArgs*, float*, int*, float*, long long,
                          int, hipStream_t);
 int launch_proba_smooth(const float*, float*, int*, const int*, float, float,
                         int*, float*, long long, int, hipStream_t);
+int class_traffic_blocks(long long);
+int launch_class_traffic(const float*, const int*, const float*, const int*,
+                         float, double*, double*, long long, int, int,
+                         hipStream_t);
 int launch_svc_predict(const float*, const float*, const float*,
                        const unsigned char*, const float*, int*, long long,
                        int, int, float, hipStream_t);
@@ -363,6 +367,55 @@ static std::vector<torch::Tensor> proba_smooth(
       cur_stream());
   TORCH_CHECK(rc == 0, "proba_smooth: arguments out of the kernel's range");
   return {labels, conf};
+}
+
+// Returns totals [C + 1, 13] f64: per group (class, or C for "unknown") the
+// row count and the f64 sums of the 12 features.  `conf` is an f32 [n] tensor
+// or None, `n_live` an int32 [1] tensor or None (all n rows are live).
+static torch::Tensor class_traffic(torch::Tensor X, torch::Tensor labels,
+                                   int64_t n_classes,
+                                   c10::optional<torch::Tensor> conf,
+                                   double min_conf,
+                                   c10::optional<torch::Tensor> n_live) {
+  CHECK_IN(X, torch::kFloat32);
+  CHECK_IN(labels, torch::kInt32);
+  TORCH_CHECK(X.dim() == 2 && X.size(1) == 12, "X must be (n,12)");
+  const long long n = X.size(0);
+  TORCH_CHECK(labels.dim() == 1 && labels.size(0) == n, "labels must be (n)");
+  TORCH_CHECK(labels.get_device() == X.get_device(),
+              "X and labels must be on one device");
+  TORCH_CHECK(n_classes >= 2 && n_classes <= 8,
+              "no kernel for class_traffic with ", n_classes, " classes (2..8)");
+  const float* cf = nullptr;
+  if (conf.has_value()) {
+    const torch::Tensor& conf_t = conf.value();
+    CHECK_IN(conf_t, torch::kFloat32);
+    TORCH_CHECK(conf_t.dim() == 1 && conf_t.size(0) == n &&
+                    conf_t.get_device() == X.get_device(),
+                "conf must be an f32 (n) tensor on X's device");
+    cf = conf_t.data_ptr<float>();
+  }
+  const int* live = nullptr;
+  if (n_live.has_value()) {
+    const torch::Tensor& n_live_t = n_live.value();
+    CHECK_IN(n_live_t, torch::kInt32);
+    TORCH_CHECK(n_live_t.numel() == 1 && n_live_t.get_device() == X.get_device(),
+                "n_live must be an int32 [1] tensor on X's device");
+    live = n_live_t.data_ptr<int>();
+  }
+  const float mc = (float)min_conf;
+  TORCH_CHECK(std::isfinite(mc), "min_conf must be finite");
+  const int C = (int)n_classes;
+  const int nb = class_traffic_blocks(n);
+  const auto f64 = X.options().dtype(torch::kFloat64);
+  auto partial = torch::empty({(int64_t)nb * (C + 1) * 13}, f64);
+  auto totals = torch::empty({C + 1, 13}, f64);
+  const int rc = launch_class_traffic(
+      X.data_ptr<float>(), labels.data_ptr<int>(), cf, live, mc,
+      partial.data_ptr<double>(), totals.data_ptr<double>(), n, C, nb,
+      cur_stream());
+  TORCH_CHECK(rc == 0, "no kernel for class_traffic with ", C, " classes");
+  return totals;
 }
 
 static torch::Tensor svc_predict(torch::Tensor X, torch::Tensor SV,
@@ -796,6 +849,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "per-flow moving average of a probability row: (labels, conf)",
         py::arg("proba"), py::arg("state"), py::arg("held"), py::arg("n_live"),
         py::arg("alpha"), py::arg("margin"));
+  m.def("class_traffic", &class_traffic,
+        "per-class flow count and f64 feature sums: totals [C + 1, 13]",
+        py::arg("X"), py::arg("labels"), py::arg("n_classes"), py::arg("conf"),
+        py::arg("min_conf"), py::arg("n_live"));
   m.def("svc_predict", &svc_predict, "RBF Gram + OVO vote");
   m.def("svc_decision", &svc_decision, "RBF Gram + OVO decision values (f64)");
   m.def("svc_couple", &svc_couple,

@@ -12,6 +12,7 @@ from __future__ import annotations
 import torch
 
 from . import cpu as _cpu
+from .cpu import TRAFFIC_COLUMNS  # noqa: F401  (a constant, not an op to dispatch)
 
 _gpu = None
 _gpu_err: Exception | None = None

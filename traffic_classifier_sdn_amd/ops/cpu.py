@@ -14,6 +14,8 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
+from ..utils.schema import FEATURE_NAMES as _FEATURE_NAMES
+
 
 # ----------------------------------------------------------------------
 # Linear / logistic (N1)
@@ -718,6 +720,105 @@ def proba_smooth(
     state[:n] = torch.where(live.unsqueeze(1), s, torch.zeros_like(s))
     held[:n] = torch.where(live, label, torch.full_like(label, -1)).to(torch.int32)
     return label.to(torch.int32), conf
+
+
+# ----------------------------------------------------------------------
+# Per-class traffic accounting
+# ----------------------------------------------------------------------
+
+# the columns of class_traffic's totals
+TRAFFIC_COLUMNS = ("flows",) + _FEATURE_NAMES
+
+
+def class_traffic_check(X, labels, n_classes, conf, min_conf, n_live):
+    """Argument rules of class_traffic, shared by the CPU and GPU bindings.
+    Returns (C, min_conf) with min_conf a Python float holding f32(min_conf),
+    the value a confidence is compared with."""
+    for name, t in (("X", X), ("labels", labels)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"class_traffic takes tensors, got {type(t).__name__} for {name}")
+    if isinstance(n_classes, bool) or not isinstance(n_classes, (int, np.integer)):
+        raise ValueError(f"n_classes must be an int, got {n_classes!r}")
+    C = int(n_classes)
+    if not 2 <= C <= 8:
+        raise ValueError(f"class_traffic supports 2..8 classes, got {C}")
+    if X.dim() != 2 or X.shape[1] != len(_FEATURE_NAMES):
+        raise ValueError(f"class_traffic takes (n, 12) features, got {tuple(X.shape)}")
+    n = X.shape[0]
+    if tuple(labels.shape) != (n,):
+        raise ValueError(f"class_traffic takes labels ({n},), got {tuple(labels.shape)}")
+    if X.dtype != torch.float32 or labels.dtype != torch.int32:
+        raise ValueError("class_traffic takes f32 X and int32 labels")
+    if not (X.is_contiguous() and labels.is_contiguous()):
+        raise ValueError("X and labels must be contiguous")
+    if labels.device != X.device:
+        raise ValueError("X and labels must be on one device")
+    if conf is not None:
+        if (
+            not isinstance(conf, torch.Tensor)
+            or conf.dtype != torch.float32
+            or tuple(conf.shape) != (n,)
+            or not conf.is_contiguous()
+            or conf.device != X.device
+        ):
+            raise ValueError(f"conf must be None or a contiguous f32 ({n},) tensor on X's device")
+    if n_live is not None:
+        if (
+            not isinstance(n_live, torch.Tensor)
+            or n_live.dtype != torch.int32
+            or tuple(n_live.shape) != (1,)
+            or n_live.device != X.device
+        ):
+            raise ValueError("n_live must be None or an int32 [1] tensor on X's device")
+    with np.errstate(over="ignore"):
+        m = np.float32(min_conf)
+    if not np.isfinite(float(min_conf)) or not bool(np.isfinite(m)):
+        raise ValueError(f"min_conf must be finite, got {min_conf}")
+    return C, float(m)
+
+
+def class_traffic(
+    X: torch.Tensor,
+    labels: torch.Tensor,
+    n_classes: int,
+    conf: Optional[torch.Tensor] = None,
+    min_conf: float = 0.0,
+    n_live: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Per-class flow count and feature sums: totals [C + 1, 13] f64, the
+    columns TRAFFIC_COLUMNS.
+
+    Row r < min(n, n_live[0]) belongs to group labels[r], or to group C
+    ("unknown") when its label is outside 0..C-1 or ``conf`` is given and
+    conf[r] < f32(min_conf) (false for a NaN confidence).  totals[g, 0]
+    counts the group's rows and totals[g, 1 + j] sums (double)X[r, j] over
+    them.  Rows at or past n_live[0] contribute nothing; every cell is
+    written, zeros included.
+
+    A plain index_add_: a NaN or infinity reaches the one cell of its row's
+    group and column.  Dead rows go to a spare group that is cut off, not
+    through a 0/1 factor.  Nothing here reads a value back to the host, so
+    the same formulation runs on device tensors.
+    """
+    C, mc = class_traffic_check(X, labels, n_classes, conf, min_conf, n_live)
+    n = X.shape[0]
+    dev = X.device
+    totals = torch.zeros(C + 2, len(TRAFFIC_COLUMNS), dtype=torch.float64, device=dev)
+    if n == 0:
+        return totals[: C + 1]
+    lab = labels.long()
+    known = (lab >= 0) & (lab < C)
+    if conf is not None:
+        known &= ~(conf < mc)
+    g = torch.where(known, lab, torch.full_like(lab, C))
+    if n_live is not None:
+        live = torch.arange(n, device=dev) < n_live.long()
+        g = torch.where(live, g, torch.full_like(g, C + 1))
+    vals = torch.cat(
+        [torch.ones(n, 1, dtype=torch.float64, device=dev), X.double()], dim=1
+    )
+    totals.index_add_(0, g, vals)
+    return totals[: C + 1]
 
 
 # ----------------------------------------------------------------------

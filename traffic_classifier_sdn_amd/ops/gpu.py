@@ -485,6 +485,23 @@ def proba_smooth(
     return labels, conf
 
 
+class_traffic_check = _cpu.class_traffic_check
+TRAFFIC_COLUMNS = _cpu.TRAFFIC_COLUMNS
+
+
+def class_traffic(
+    X: torch.Tensor,
+    labels: torch.Tensor,
+    n_classes: int,
+    conf: Optional[torch.Tensor] = None,
+    min_conf: float = 0.0,
+    n_live: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    # no cast and no copy: the captured serve pass hands its own buffers over
+    C, mc = _cpu.class_traffic_check(X, labels, n_classes, conf, min_conf, n_live)
+    return _ext.class_traffic(X, labels, C, conf, mc, n_live)
+
+
 # ----------------------------------------------------------------------
 # fit ops
 # ----------------------------------------------------------------------

@@ -44,6 +44,46 @@ def render_flow_table(table: FlowTable, labels, confidence=None) -> str:
     return str(t)
 
 
+# (heading, key in a --stats line, column of the totals) of the summary's rates:
+# the four instantaneous-rate features
+_SUMMARY_RATES = (
+    ("Fwd pkt/s", "fwd_pps", "Forward Instantaneous Packets per Second"),
+    ("Fwd B/s", "fwd_Bps", "Forward Instantaneous Bytes per Second"),
+    ("Rev pkt/s", "rev_pps", "DeltaReverse Instantaneous Packets per Second"),
+    ("Rev B/s", "rev_Bps", "Reverse Instantaneous Bytes per Second"),
+)
+
+
+def traffic_rates(classes, totals) -> dict:
+    """{class: {flows, fwd_pps, fwd_Bps, rev_pps, rev_Bps}} out of the totals
+    of ops.class_traffic (rows: ``classes``, the last one "unknown")."""
+    from .ops.cpu import TRAFFIC_COLUMNS
+
+    cols = [(key, TRAFFIC_COLUMNS.index(name)) for _, key, name in _SUMMARY_RATES]
+    out = {}
+    for g, name in enumerate(classes):
+        row = {"flows": int(totals[g, 0])}
+        row.update({key: float(totals[g, c]) for key, c in cols})
+        out[name] = row
+    return out
+
+
+def render_traffic_summary(classes, totals) -> str:
+    """The per-class table below the flow table: one row per class and
+    "unknown", also where a class has no flows."""
+    rates = traffic_rates(classes, totals)
+    total_bytes = sum(r["fwd_Bps"] + r["rev_Bps"] for r in rates.values())
+    t = Table(["Traffic Type", "Flows"] + [h for h, _, _ in _SUMMARY_RATES] + ["Bytes share"])
+    for name, r in rates.items():
+        share = (r["fwd_Bps"] + r["rev_Bps"]) / total_bytes if total_bytes != 0 else 0.0
+        t.add_row(
+            [name, r["flows"]]
+            + ["%.1f" % r[key] for _, key, _ in _SUMMARY_RATES]
+            + ["%.1f%%" % (100.0 * share)]
+        )
+    return str(t)
+
+
 def map_cluster_labels(idx: np.ndarray) -> np.ndarray:
     """Integer cluster ids -> class names (reference label map,
     traffic_classifier.py:109-114)."""
@@ -71,8 +111,31 @@ class RealtimeClassifier:
         min_confidence: float = 0.0,
         smooth: Optional[float] = None,
         switch_margin: float = 0.0,
+        summary: bool = False,
+        prometheus_registry=None,
     ) -> None:
         self.model = model
+        # summary=True: flows, packets/s and bytes/s per class after each
+        # pass (ops.class_traffic on the model's device), as a second table,
+        # in the --stats line and in the Prometheus gauges
+        self.summary = bool(summary)
+        self.traffic: Optional[np.ndarray] = None  # f64 [C + 1, 13] of the last pass
+        self.traffic_classes: Optional[list] = None
+        if self.summary:
+            names = getattr(model, "classes_", None)
+            if names is None:
+                names = getattr(model, "cluster_label_names_", None)
+            if names is None:
+                names = CLASS_NAMES
+            # a cluster map may give two clusters one name
+            names = [n for n in dict.fromkeys(str(n) for n in names) if n != "unknown"]
+            if not 2 <= len(names) <= 8:
+                raise ValueError(
+                    f"summary accounts 2..8 classes, {type(model).__name__} has {len(names)}"
+                )
+            self.traffic_classes = names + ["unknown"]
+            self._class_index = {n: i for i, n in enumerate(names)}
+            self._last_X = np.zeros((0, 12), dtype=np.float32)
         # smooth=alpha: labels and confidence come from the flow's class
         # probabilities averaged across passes (models/smoothing.py)
         self.smoother = None
@@ -102,15 +165,21 @@ class RealtimeClassifier:
         if prometheus_port:
             from .utils.prom import PromServeMetrics
 
-            self.prom = PromServeMetrics(prometheus_port)
+            self.prom = PromServeMetrics(
+                prometheus_port, registry=prometheus_registry, summary=self.summary
+            )
 
     def classify_now(self) -> np.ndarray:
         table = self.parser.table
         if len(table) == 0:
             if self.confidence:
                 self.last_confidence = np.zeros(0, dtype=np.float32)
+            if self.summary:
+                self._last_X = np.zeros((0, 12), dtype=np.float32)
             return np.asarray([], dtype=object)
         X = table.feature_matrix(dtype=np.float32)
+        if self.summary:
+            self._last_X = X
         if self.smoother is not None:
             return self._classify_smoothed(X)
         if self.confidence:
@@ -147,6 +216,24 @@ class RealtimeClassifier:
             pred[conf < self.min_confidence] = "unknown"
         return pred
 
+    def account(self, labels) -> np.ndarray:
+        """Totals [C + 1, 13] of the pass that gave ``labels`` (names, with
+        "unknown" already applied): summed on the model's device."""
+        import torch
+
+        from . import ops
+
+        C = len(self.traffic_classes) - 1
+        device = torch.device(str(getattr(self.model, "device", "cpu")))
+        idx = np.fromiter(
+            (self._class_index.get(str(name), C) for name in labels),
+            dtype=np.int32, count=len(labels),
+        )
+        X = torch.from_numpy(np.ascontiguousarray(self._last_X)).to(device)
+        totals = ops.class_traffic(X, torch.from_numpy(idx).to(device), C)
+        self.traffic = totals.cpu().numpy()
+        return self.traffic
+
     def feed(self, line) -> bool:
         """Feed one telemetry line; returns True when a prediction pass ran.
 
@@ -165,11 +252,16 @@ class RealtimeClassifier:
             predict_s = time.perf_counter() - t0
             conf = self.last_confidence if self.confidence else None
             self.out.write(render_flow_table(self.parser.table, labels, conf) + "\n")
+            if self.summary:
+                totals = self.account(labels)
+                self.out.write(render_traffic_summary(self.traffic_classes, totals) + "\n")
             self.out.flush()
             if self.prom is not None:
                 self.prom.observe_pass(
                     len(self.parser.table), self.parser.records, predict_s, labels
                 )
+                if self.summary:
+                    self.prom.observe_traffic(traffic_rates(self.traffic_classes, totals))
             if self.stats:
                 n = len(self.parser.table)
                 line = {
@@ -182,6 +274,8 @@ class RealtimeClassifier:
                 if conf is not None:
                     line["mean_confidence"] = float(conf.mean()) if n else None
                     line["unknown"] = int((conf < self.min_confidence).sum())
+                if self.summary:
+                    line["traffic"] = traffic_rates(self.traffic_classes, totals)
                 self.stats_out.write(json.dumps(line) + "\n")
                 self.stats_out.flush()
             return True

@@ -24,6 +24,15 @@ the smoothed probability of that label.  ``"ensemble"`` stays the raw vote.
 The smoothing kernel is part of the captured graph too; the live-row count
 reaches it through device memory, so that the rows past it, which the graph
 also runs over, are reset and not averaged.
+
+``traffic=key`` accounts the pass per class of that key's labels (a
+supervised model's name, ``"ensemble"`` or ``"smoothed"``): after
+``classify``, ``engine.traffic`` holds the f64 [C + 1, 13] totals of
+ops.class_traffic, flow count and the 12 feature sums per class and for
+``"unknown"`` (``engine.traffic_classes``).  With ``traffic_min_confidence``
+a flow whose confidence is below it counts as unknown.  The reduction runs
+in the captured graph on the features that exist only on the device; one
+table of under 1 KB comes back instead of them.
 """
 
 from __future__ import annotations
@@ -39,6 +48,13 @@ from .models.base import Estimator
 
 
 class GpuServeEngine:
+    # set per instance only with traffic=, so that an engine without it is
+    # what it was: after classify(), f64 [C + 1, 13] totals of the pass (rows:
+    # traffic_classes, columns: ops.TRAFFIC_COLUMNS)
+    traffic: Optional[np.ndarray] = None
+    traffic_classes: Optional[List[str]] = None
+    _traffic_key: Optional[str] = None
+
     def __init__(
         self,
         models: Dict[str, Estimator],
@@ -50,6 +66,8 @@ class GpuServeEngine:
         ensemble_weights: Optional[Sequence[float]] = None,
         smooth: Optional[float] = None,
         switch_margin: float = 0.0,
+        traffic: Optional[str] = None,
+        traffic_min_confidence: float = 0.0,
     ) -> None:
         self.models = models
         self.capacity = capacity
@@ -109,11 +127,6 @@ class GpuServeEngine:
             self.smoother = FlowSmoother(
                 len(self.ensemble.classes_), capacity, smooth, switch_margin, device=self.device
             )
-            # the live-row count, staged like the counters: the captured
-            # pass runs over all `capacity` rows and reads it on the device
-            self.h_nlive = torch.zeros(1, dtype=torch.int32, pin_memory=pin)
-            self._h_nlive_np = self.h_nlive.numpy()  # same memory, cheap to set
-            self.d_nlive = torch.zeros(1, dtype=torch.int32, device=self.device)
             self._smooth_table: Optional[FlowTable] = None
             self._smooth_n = 0
         # the keys the vote adds to the result, and every key of
@@ -122,6 +135,46 @@ class GpuServeEngine:
             ["smoothed"] if self.smoother else []
         )
         self._conf_keys = self._conf_models + self._vote_keys
+        # per-class accounting of one key's labels (ops.class_traffic)
+        if traffic is not None:
+            if traffic in self._vote_keys:
+                classes = self.ensemble.classes_
+            elif traffic in models:
+                classes = getattr(models[traffic], "classes_", None)
+                if classes is None:
+                    raise ValueError(
+                        f"traffic={traffic!r}: {type(models[traffic]).__name__} has no classes "
+                        "to account by"
+                    )
+            elif traffic in ("ensemble", "smoothed"):
+                raise ValueError(
+                    f"traffic={traffic!r} needs "
+                    + ("ensemble=" if traffic == "ensemble" else "smooth=")
+                )
+            else:
+                raise ValueError(f"traffic={traffic!r} is not a key of the result")
+            if not 2 <= len(classes) <= 8:
+                raise ValueError(f"traffic= accounts 2..8 classes, {traffic!r} has {len(classes)}")
+            mc = float(traffic_min_confidence)
+            if not np.isfinite(mc) or mc < 0.0:
+                raise ValueError(f"traffic_min_confidence must be finite and >= 0, got {mc}")
+            if mc > 0.0 and traffic not in self._conf_keys:
+                raise ValueError(
+                    f"traffic_min_confidence needs a confidence, and {traffic!r} has none "
+                    "(confidence=True and a model with predict_index_conf, the vote or the "
+                    "smoothed verdict)"
+                )
+            self._traffic_key = traffic
+            self._traffic_min_conf = mc
+            self.traffic_classes = [str(c) for c in classes] + ["unknown"]
+            self._d_traffic: Optional[torch.Tensor] = None
+            self._h_traffic: Optional[torch.Tensor] = None
+        if self.smoother is not None or traffic is not None:
+            # the live-row count, staged like the counters: the captured
+            # pass runs over all `capacity` rows and reads it on the device
+            self.h_nlive = torch.zeros(1, dtype=torch.int32, pin_memory=pin)
+            self._h_nlive_np = self.h_nlive.numpy()  # same memory, cheap to set
+            self.d_nlive = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.confidence: Dict[str, np.ndarray] = {}
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self.last_latency_s = 0.0
@@ -131,11 +184,33 @@ class GpuServeEngine:
         from . import ops
 
         X = ops.flow_features(self.d_cur, self.d_prev, self.d_times)
-        n_live = self.d_nlive if self.smoother is not None else None
+        staged = self.smoother is not None or self._traffic_key is not None
+        n_live = self.d_nlive if staged else None
         for name, labels, conf in self._predict_all(X, n_live):
             if conf is not None:
                 self._keep(self.d_conf, self.h_conf, name, conf)
             self._keep(self.d_labels, self.h_labels, name, labels)
+            if name == self._traffic_key:
+                # rows past the live count hold counters of earlier polls
+                totals = self._account(X, labels, conf, n_live)
+                if self._d_traffic is None:
+                    self._d_traffic = totals
+                    self._h_traffic = torch.empty_like(
+                        totals, device="cpu", pin_memory=self.device.type == "cuda"
+                    )
+                else:
+                    self._d_traffic.copy_(totals)
+
+    def _account(self, X: torch.Tensor, labels: torch.Tensor,
+                 conf: Optional[torch.Tensor], n_live: Optional[torch.Tensor]) -> torch.Tensor:
+        from . import ops
+
+        if labels.dtype != torch.int32:  # a CPU model's int64 argmax
+            labels = labels.to(torch.int32)
+        mc = self._traffic_min_conf
+        return ops.class_traffic(
+            X, labels, len(self.traffic_classes) - 1, conf if mc > 0.0 else None, mc, n_live
+        )
 
     def _keep(self, dev: Dict[str, torch.Tensor], host: Dict[str, torch.Tensor],
               name: str, value: torch.Tensor) -> None:
@@ -221,7 +296,7 @@ class GpuServeEngine:
             self._smooth_begin(table, n)
         if n > self.capacity:
             return self._classify_unbounded(table)
-        if self.smoother is not None:
+        if self.smoother is not None or self._traffic_key is not None:
             self._h_nlive_np[0] = n
             self.d_nlive.copy_(self.h_nlive, non_blocking=True)
         cur, prev, times = table.counters_snapshot()
@@ -244,12 +319,16 @@ class GpuServeEngine:
                 self.h_labels[name].copy_(self.d_labels[name], non_blocking=True)
             for name in self._conf_keys:
                 self.h_conf[name].copy_(self.d_conf[name], non_blocking=True)
+            if self._traffic_key is not None:
+                self._h_traffic.copy_(self._d_traffic, non_blocking=True)
             torch.cuda.synchronize()
             for name in keys:
                 out[name] = self.h_labels[name][:n].numpy().copy()
             self.confidence = {
                 name: self.h_conf[name][:n].numpy().copy() for name in self._conf_keys
             }
+            if self._traffic_key is not None:
+                self.traffic = self._h_traffic.numpy().copy()
         else:
             self.d_cur.copy_(self.h_cur)
             self.d_prev.copy_(self.h_prev)
@@ -259,6 +338,8 @@ class GpuServeEngine:
             self.confidence = {
                 name: self.d_conf[name][:n].numpy().copy() for name in self._conf_keys
             }
+            if self._traffic_key is not None:
+                self.traffic = self._d_traffic.numpy().copy()
         self.last_latency_s = time.perf_counter() - t0
         return out
 
@@ -277,5 +358,7 @@ class GpuServeEngine:
             if conf is not None:
                 self.confidence[name] = conf.cpu().numpy()
             out[name] = labels.cpu().numpy()
+            if name == self._traffic_key:  # every row of X is a live flow
+                self.traffic = self._account(X, labels, conf, None).cpu().numpy()
         self.last_latency_s = time.perf_counter() - t0
         return out
