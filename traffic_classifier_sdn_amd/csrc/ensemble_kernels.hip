@@ -22,7 +22,7 @@
 #include <cstdlib>
 
 #include "common.h"
-#include "ensemble.h"
+#include "launchers.h"
 
 #define PROBA_BLOCK 256
 

@@ -6,6 +6,7 @@
 #include <cfloat>
 
 #include "common.h"
+#include "launchers.h"
 
 // ---------------------------------------------------------------------------
 // GaussianNB sufficient stats: per-class (count, sum, sum-of-squares).
@@ -53,9 +54,8 @@ extern "C" void launch_gnb_fit_stats(const double* X, const long long* y,
                                      double* count, double* sum, double* sumsq,
                                      long long n, int C, hipStream_t stream) {
   const int block = 256;
-  size_t lds = (size_t)(2 * C * 12 + C) * sizeof(double);
   hipLaunchKernelGGL(gnb_fit_stats_kernel, dim3(ts_grid(n, block)), dim3(block),
-                     lds, stream, X, y, count, sum, sumsq, n, C);
+                     gnb_fit_stats_lds_bytes(C), stream, X, y, count, sum, sumsq, n, C);
 }
 
 // ---------------------------------------------------------------------------
@@ -160,14 +160,17 @@ __global__ void logistic_grad_kernel(const double* __restrict__ X,
   }
 }
 
-extern "C" void launch_logistic_grad(const double* X, const long long* y,
-                                     const double* W, const double* b,
-                                     double* grad, double* loss, long long n,
-                                     int C, hipStream_t stream) {
+// Returns 0, or nonzero when no kernel exists for C classes (nothing is
+// launched: the caller must turn that into an error); so do launch_rf_split
+// and launch_rf_split_compact.
+extern "C" int launch_logistic_grad(const double* X, const long long* y,
+                                    const double* W, const double* b,
+                                    double* grad, double* loss, long long n,
+                                    int C, hipStream_t stream) {
   const int block = 256;
   size_t bytes = (size_t)(C * 12 + C + (block / 64) * C * 13) * sizeof(double);
   dim3 grid(ts_grid(n, block));
-  dispatch_int<2, 3, 4, 5, 6, 7, 8, 12, 16>(C, [&](auto c) {
+  return !dispatch_int<2, 3, 4, 5, 6, 7, 8, 12, 16>(C, [&](auto c) {
     hipLaunchKernelGGL((logistic_grad_kernel<decltype(c)::value>), grid,
                        dim3(block), bytes, stream, X, y, W, b, grad, loss, n);
   });
@@ -399,13 +402,13 @@ extern "C" void launch_rf_partition(const unsigned char* B, int* nid,
                      0, stream, B, nid, lmap, feat, binthr, n);
 }
 
-extern "C" void launch_rf_split(const int* hist, const unsigned char* fsel,
-                                unsigned long long* best, int* cnt, int L,
-                                int C, hipStream_t stream) {
+extern "C" int launch_rf_split(const int* hist, const unsigned char* fsel,
+                               unsigned long long* best, int* cnt, int L,
+                               int C, hipStream_t stream) {
   const int block = 256;
   long long work = (long long)L * 12;
   dim3 grid((unsigned)((work + block - 1) / block));
-  dispatch_int<2, 3, 4, 5, 6, 7, 8, 12, 16>(C, [&](auto c) {
+  return !dispatch_int<2, 3, 4, 5, 6, 7, 8, 12, 16>(C, [&](auto c) {
     hipLaunchKernelGGL((rf_split_kernel<decltype(c)::value>), grid, dim3(block),
                        0, stream, hist, fsel, best, cnt, L);
   });
@@ -949,15 +952,15 @@ __global__ void rf_split_compact_kernel(const int* __restrict__ hist,
   atomicMin(&best[node], p);
 }
 
-extern "C" void launch_rf_split_compact(const int* hist,
-                                        const unsigned char* fidx,
-                                        unsigned long long* best, int* cnt,
-                                        int L, int C, int mf,
-                                        hipStream_t stream) {
+extern "C" int launch_rf_split_compact(const int* hist,
+                                       const unsigned char* fidx,
+                                       unsigned long long* best, int* cnt,
+                                       int L, int C, int mf,
+                                       hipStream_t stream) {
   const int block = 256;
   long long work = (long long)L * mf;
   dim3 grid((unsigned)((work + block - 1) / block));
-  dispatch_int<2, 3, 4, 5, 6, 7, 8, 12, 16>(C, [&](auto c) {
+  return !dispatch_int<2, 3, 4, 5, 6, 7, 8, 12, 16>(C, [&](auto c) {
     hipLaunchKernelGGL((rf_split_compact_kernel<decltype(c)::value>), grid,
                        dim3(block), 0, stream, hist, fidx, best, cnt, L, mf);
   });

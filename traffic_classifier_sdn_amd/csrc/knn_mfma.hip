@@ -42,6 +42,7 @@
 #include <cfloat>
 
 #include "common.h"
+#include "launchers.h"
 
 #define KM_NQT 2       // query groups per wave
 #define KM_QB (32 * 4 * KM_NQT)  // queries per workgroup

@@ -15,6 +15,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "launchers.h"
 
 // ---------------------------------------------------------------------------
 // Gaussian NB: fused joint-log-likelihood + argmax (reference N5).
@@ -64,9 +65,8 @@ extern "C" void launch_gnb_predict(const float* X, const float* theta,
                                    int* out, long long n, int C,
                                    hipStream_t stream) {
   const int block = 256;
-  size_t lds = (size_t)(2 * C * 12 + C) * sizeof(float);
   hipLaunchKernelGGL(gnb_predict_kernel, dim3(ts_grid(n, block)), dim3(block),
-                     lds, stream, X, theta, inv_var, cconst, out, n, C);
+                     gnb_predict_lds_bytes(C), stream, X, theta, inv_var, cconst, out, n, C);
 }
 
 // ---------------------------------------------------------------------------
@@ -105,9 +105,8 @@ extern "C" void launch_linear_argmax(const float* X, const float* W,
                                      const float* b, int* out, long long n,
                                      int C, hipStream_t stream) {
   const int block = 256;
-  size_t lds = (size_t)(C * 12 + C) * sizeof(float);
   hipLaunchKernelGGL(linear_argmax_kernel, dim3(ts_grid(n, block)), dim3(block),
-                     lds, stream, X, W, b, out, n, C);
+                     linear_argmax_lds_bytes(C), stream, X, W, b, out, n, C);
 }
 
 // ---------------------------------------------------------------------------
@@ -177,10 +176,8 @@ extern "C" void launch_kmeans_assign(const float* X, const float* centers,
                                      double* inertia, long long n, int K,
                                      int want_update, hipStream_t stream) {
   const int block = 256;
-  size_t lds = (size_t)(K * 12 + K) * sizeof(double) +
-               (size_t)(K * 12) * sizeof(float);
   hipLaunchKernelGGL(kmeans_assign_kernel, dim3(ts_grid(n, block)), dim3(block),
-                     lds, stream, X, centers, labels, counts, sums, inertia, n,
+                     kmeans_assign_lds_bytes(K), stream, X, centers, labels, counts, sums, inertia, n,
                      K, want_update);
 }
 

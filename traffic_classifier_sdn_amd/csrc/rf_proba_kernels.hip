@@ -20,6 +20,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "launchers.h"
 
 // Label and confidence from the C sums.
 template <int C>

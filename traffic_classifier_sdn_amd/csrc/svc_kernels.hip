@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "launchers.h"
 
 #define SVC_TILE 128
 #define SVC_BLOCK 256

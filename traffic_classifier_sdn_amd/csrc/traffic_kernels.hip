@@ -40,6 +40,7 @@
 // Bytes read per row: 48 of features, 4 of label, 4 of confidence if given.
 
 #include "common.h"
+#include "launchers.h"
 
 #define TRAFFIC_BLOCK 256
 #define TRAFFIC_COLS 13        // flow count + 12 features

@@ -30,16 +30,29 @@ def _f32(t: torch.Tensor) -> torch.Tensor:
     return t.to(torch.float32).contiguous()
 
 
-# Model parameters are fixed between fits, but a `.to(float32)` per predict
-# call launches a conversion kernel every time — inside the hipGraph-captured
-# serve path that was ~9 stray elementwise kernels per replay.  Cache the
-# converted copies keyed by source buffer address, and keep a reference to
-# the SOURCE tensor in the entry: torch's caching allocator reuses freed
-# addresses, so a data_ptr key alone could serve a stale cast after a model
-# is freed and a same-shape tensor lands at the recycled address (ADVICE
-# r01).  Pinning the source keeps its address out of the free pool for the
-# lifetime of the entry, which makes the (ptr, numel, dtype) key unambiguous
-# (the models never mutate parameters in place).
+# Model parameters are fixed between fits, but a `.to(float32)` or a derived
+# constant per predict call launches a kernel every time — inside the
+# hipGraph-captured serve path that was ~9 stray elementwise kernels per
+# replay.  The caches below keep such tensors keyed by source buffer address,
+# and every entry holds a reference to its SOURCE tensors: torch's caching
+# allocator reuses freed addresses, so a data_ptr key alone could serve a
+# stale value after a model is freed and a same-shape tensor lands at the
+# recycled address.  Pinning the sources keeps their addresses
+# out of the free pool for the lifetime of the entry, which makes the key
+# unambiguous (the models never mutate parameters in place).
+def _cached(cache: dict, cap: int, key: tuple, sources: tuple, build) -> tuple:
+    """The entry ``(*sources, *build())`` of ``cache`` under ``key``, built on
+    a miss; a cache past ``cap`` entries is cleared first."""
+    ent = cache.get(key)
+    if ent is None:
+        if len(cache) > cap:
+            cache.clear()
+        ent = (*sources, *build())
+        cache[key] = ent
+    return ent
+
+
+# entry = (source, f32 copy)
 _cast_cache: Dict[Tuple[int, int, torch.dtype], Tuple[torch.Tensor, torch.Tensor]] = {}
 
 
@@ -47,13 +60,7 @@ def _f32_cached(t: torch.Tensor) -> torch.Tensor:
     if t.dtype == torch.float32 and t.is_contiguous():
         return t
     key = (t.data_ptr(), t.numel(), t.dtype)
-    ent = _cast_cache.get(key)
-    if ent is None:
-        if len(_cast_cache) > 64:
-            _cast_cache.clear()
-        ent = (t, t.to(torch.float32).contiguous())
-        _cast_cache[key] = ent
-    return ent[1]
+    return _cached(_cast_cache, 64, key, (t,), lambda: (_f32(t),))[1]
 
 
 def _f64(t: torch.Tensor) -> torch.Tensor:
@@ -71,10 +78,15 @@ def linear_argmax(X: torch.Tensor, coef: torch.Tensor, intercept: torch.Tensor) 
     return _ext.linear_argmax(_f32(X), _f32_cached(coef), _f32_cached(intercept))
 
 
-# entry = (var_ref, prior_ref, theta32, inv_var, const32): the first two pin
-# the source buffers so their addresses cannot be recycled while cached
-# (same aliasing hazard as _cast_cache)
+# entry = (var, prior, theta32, inv_var, const32)
 _gnb_cache: Dict[Tuple[int, int], Tuple[torch.Tensor, ...]] = {}
+
+
+def _gnb_consts(var: torch.Tensor, class_prior: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(1 / var, log prior - 0.5 * sum log(2 pi var)), both f64."""
+    var64 = var.double()
+    const = torch.log(class_prior.double()) - 0.5 * torch.log(2.0 * torch.pi * var64).sum(dim=1)
+    return (1.0 / var64).contiguous(), const.contiguous()
 
 
 def gnb_argmax(
@@ -85,16 +97,11 @@ def gnb_argmax(
     if X.shape[1] != 12:
         return _cpu.gnb_argmax(X, theta, var, class_prior)
     key = (var.data_ptr(), class_prior.data_ptr())
-    ent = _gnb_cache.get(key)
-    if ent is None:
-        if len(_gnb_cache) > 32:
-            _gnb_cache.clear()
-        var64 = var.double()
-        const = (torch.log(class_prior.double()) - 0.5 * torch.log(2.0 * torch.pi * var64).sum(dim=1))
-        ent = (var, class_prior, _f32(theta), (1.0 / var64).float().contiguous(), const.float().contiguous())
-        _gnb_cache[key] = ent
-    _, _, theta32, inv_var, const32 = ent
-    return _ext.gnb_predict(_f32(X), theta32, inv_var, const32)
+    ent = _cached(
+        _gnb_cache, 32, key, (var, class_prior),
+        lambda: (_f32(theta), *(t.float() for t in _gnb_consts(var, class_prior))),
+    )
+    return _ext.gnb_predict(_f32(X), *ent[2:])
 
 
 def kmeans_assign(
@@ -111,8 +118,7 @@ def kmeans_assign(
 # launch simplicity wins; above it the v_mfma_f32_32x32x2_f32 distance
 # GEMM dominates (csrc/knn_mfma.hip)
 _KNN_MFMA_MIN_ROWS = 100_000
-# entry = (R_ref, cmean): R_ref pins the reference buffer against address
-# recycling
+# entry = (R, cmean)
 _knn_cmean_cache: Dict[Tuple[int, int], Tuple[torch.Tensor, torch.Tensor]] = {}
 
 
@@ -120,13 +126,7 @@ def _knn_cmean(R: torch.Tensor) -> torch.Tensor:
     """Reference column means (centering makes the expanded-form distance
     cancellation-safe); cached per reference buffer."""
     key = (R.data_ptr(), R.shape[0])
-    ent = _knn_cmean_cache.get(key)
-    if ent is None:
-        if len(_knn_cmean_cache) > 16:
-            _knn_cmean_cache.clear()
-        ent = (R, R.mean(dim=0).float().contiguous())
-        _knn_cmean_cache[key] = ent
-    return ent[1]
+    return _cached(_knn_cmean_cache, 16, key, (R,), lambda: (R.mean(dim=0).float().contiguous(),))[1]
 
 
 def _knn_shards(nr: int) -> int:
@@ -172,6 +172,21 @@ def knn_classify(
     return dist, idx, lab
 
 
+def _svc_args(X, SV, dual_coef, intercept, n_support, gamma, svclass):
+    """The arguments of the extension's svc_predict and svc_decision."""
+    if svclass is None:
+        # the class of every support vector: static per model; callers on the
+        # hipGraph path precompute it (repeat_interleave is not stream-capture
+        # safe)
+        svclass = torch.repeat_interleave(
+            torch.arange(n_support.numel(), device=X.device), n_support.to(X.device)
+        ).to(torch.uint8)
+    return (
+        _f32(X), _f32_cached(SV), _f32_cached(dual_coef), svclass.contiguous(),
+        _f32_cached(intercept), float(gamma),
+    )
+
+
 def svc_predict(
     X: torch.Tensor,
     SV: torch.Tensor,
@@ -183,16 +198,7 @@ def svc_predict(
 ) -> torch.Tensor:
     if X.shape[1] != 12:
         return _cpu.svc_predict(X, SV, dual_coef, intercept, n_support, gamma, svclass)
-    if svclass is None:
-        # static per model; callers on the hipGraph path precompute it
-        # (repeat_interleave is not stream-capture safe)
-        svclass = torch.repeat_interleave(
-            torch.arange(n_support.numel(), device=X.device), n_support.to(X.device)
-        ).to(torch.uint8)
-    return _ext.svc_predict(
-        _f32(X), _f32_cached(SV), _f32_cached(dual_coef), svclass.contiguous(),
-        _f32_cached(intercept), float(gamma)
-    )
+    return _ext.svc_predict(*_svc_args(X, SV, dual_coef, intercept, n_support, gamma, svclass))
 
 
 # ----------------------------------------------------------------------
@@ -215,15 +221,7 @@ def svc_decision(
     ``svc_predict`` accumulates them, so their signs give its votes."""
     if X.shape[1] != 12:
         return _cpu.svc_decision(X, SV, dual_coef, intercept, n_support, gamma, svclass)
-    if svclass is None:
-        # static per model; callers on the hipGraph path precompute it
-        svclass = torch.repeat_interleave(
-            torch.arange(n_support.numel(), device=X.device), n_support.to(X.device)
-        ).to(torch.uint8)
-    return _ext.svc_decision(
-        _f32(X), _f32_cached(SV), _f32_cached(dual_coef), svclass.contiguous(),
-        _f32_cached(intercept), float(gamma)
-    )
+    return _ext.svc_decision(*_svc_args(X, SV, dual_coef, intercept, n_support, gamma, svclass))
 
 
 def svc_couple(
@@ -409,8 +407,7 @@ def rf_predict_proba(X: torch.Tensor, forest: Dict[str, torch.Tensor]) -> torch.
 ensemble_weights = _cpu.ensemble_weights
 ensemble_check = _cpu.ensemble_check
 
-# entry = (theta_ref, var_ref, prior_ref, theta64, inv_var64, const64); the
-# first three pin the source buffers, as in _gnb_cache
+# entry = (theta, var, prior, theta64, inv_var64, const64)
 _gnb_proba_cache: Dict[Tuple[int, int, int], Tuple[torch.Tensor, ...]] = {}
 
 
@@ -420,15 +417,11 @@ def gnb_proba(
     if X.shape[1] != 12:
         return _cpu.gnb_proba(X, theta, var, class_prior)
     key = (theta.data_ptr(), var.data_ptr(), class_prior.data_ptr())
-    ent = _gnb_proba_cache.get(key)
-    if ent is None:
-        if len(_gnb_proba_cache) > 32:
-            _gnb_proba_cache.clear()
-        var64 = var.double()
-        const = torch.log(class_prior.double()) - 0.5 * torch.log(2.0 * torch.pi * var64).sum(dim=1)
-        ent = (theta, var, class_prior, _f64(theta), (1.0 / var64).contiguous(), const.contiguous())
-        _gnb_proba_cache[key] = ent
-    return _ext.gnb_proba(_f32(X), ent[3], ent[4], ent[5])
+    ent = _cached(
+        _gnb_proba_cache, 32, key, (theta, var, class_prior),
+        lambda: (_f64(theta), *_gnb_consts(var, class_prior)),
+    )
+    return _ext.gnb_proba(_f32(X), *ent[3:])
 
 
 def linear_proba(X: torch.Tensor, coef: torch.Tensor, intercept: torch.Tensor) -> torch.Tensor:
@@ -437,22 +430,15 @@ def linear_proba(X: torch.Tensor, coef: torch.Tensor, intercept: torch.Tensor) -
     return _ext.linear_proba(_f32(X), _f32_cached(coef), _f32_cached(intercept))
 
 
-# entry = (y_ref, y8): y_ref pins the label buffer
+# entry = (y, y8)
 _knn_y8_cache: Dict[Tuple[int, int, torch.dtype], Tuple[torch.Tensor, torch.Tensor]] = {}
 
 
 def knn_vote_proba(idx: torch.Tensor, y: torch.Tensor, n_classes: int) -> torch.Tensor:
-    if y.dtype == torch.uint8 and y.is_contiguous():
-        y8 = y
-    else:
+    y8 = y
+    if y.dtype != torch.uint8 or not y.is_contiguous():
         key = (y.data_ptr(), y.numel(), y.dtype)
-        ent = _knn_y8_cache.get(key)
-        if ent is None:
-            if len(_knn_y8_cache) > 16:
-                _knn_y8_cache.clear()
-            ent = (y, y.to(torch.uint8).contiguous())
-            _knn_y8_cache[key] = ent
-        y8 = ent[1]
+        y8 = _cached(_knn_y8_cache, 16, key, (y,), lambda: (y.to(torch.uint8).contiguous(),))[1]
     return _ext.knn_vote_proba(idx.to(torch.int32).contiguous(), y8, int(n_classes))
 
 
