@@ -30,6 +30,7 @@ setup(
                 os.path.join(CSRC, "ext.cpp"),
                 os.path.join(CSRC, "predict_kernels.hip"),
                 os.path.join(CSRC, "rf_proba_kernels.hip"),
+                os.path.join(CSRC, "iforest_kernels.hip"),
                 os.path.join(CSRC, "ensemble_kernels.hip"),
                 os.path.join(CSRC, "traffic_kernels.hip"),
                 os.path.join(CSRC, "svc_kernels.hip"),

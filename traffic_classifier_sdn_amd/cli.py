@@ -14,6 +14,8 @@ the class probabilities of several checkpoints (models/ensemble.py).
 across passes, for every model that has them (models/smoothing.py).
 `--summary` adds a per-class table of flows, packets/s and bytes/s below
 each flow table (ops.class_traffic).
+`--novelty [--novelty-threshold S]` shows flows unlike the training data as
+'unknown', whatever the classifier says of them (models/isolation_forest.py).
 
 Telemetry sources:
   --source subprocess   spawn a monitor command (default: the in-package
@@ -113,6 +115,31 @@ def _load_ensemble(args):
         return None
 
 
+NOVELTY_CHECKPOINT = "IsolationForest.npz"
+
+
+def _load_novelty(args):
+    """The `--novelty` detector: <models-dir>/IsolationForest.npz, else the
+    in-repo one (data/ref_models), else a fit at start-up on the six-class
+    dataset, announced on stderr."""
+    from .models import IsolationForest, load_model
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for d in (args.models_dir, os.path.join(repo, "data", "ref_models")):
+        path = os.path.join(d, NOVELTY_CHECKPOINT)
+        if os.path.exists(path):
+            model = load_model(path, device=args.device)
+            if not isinstance(model, IsolationForest):
+                raise ValueError(f"{path} holds a {type(model).__name__}, not an IsolationForest")
+            return model
+    from .utils.datasets import load_six_class_dataset
+
+    print(f"NOTE: no {NOVELTY_CHECKPOINT} found: fitting the novelty detector on the "
+          "six-class dataset now", file=sys.stderr)
+    X, _ = load_six_class_dataset()
+    return IsolationForest(device=args.device).fit(X)
+
+
 def main(argv: Optional[list] = None) -> int:
     parser = argparse.ArgumentParser(
         prog="traffic_classifier_sdn_amd",
@@ -146,6 +173,13 @@ def main(argv: Optional[list] = None) -> int:
                         help="below each flow table, print flows, packets/s and bytes/s per "
                              "traffic class (summed on the model's device); adds them to --stats "
                              "and --prometheus")
+    parser.add_argument("--novelty", action="store_true",
+                        help="show flows unlike the training data as 'unknown': an isolation "
+                             "forest scores every flow on the model's device "
+                             "(<models-dir>/IsolationForest.npz, else fitted at start-up)")
+    parser.add_argument("--novelty-threshold", type=float, default=None, metavar="S",
+                        help="with --novelty: a flow is novel when its score in (0, 1) is "
+                             "above S (default: the detector's own threshold)")
     parser.add_argument("--members", default=DEFAULT_MEMBERS, metavar="A,B,...",
                         help="ensemble: the subcommand names of the member models")
     parser.add_argument("--weights", default=None, metavar="W,W,...",
@@ -202,12 +236,17 @@ def main(argv: Optional[list] = None) -> int:
         return 2
     # the streams as they are now, not as they were when serve was imported
     try:
+        if args.novelty_threshold is not None and not args.novelty:
+            raise ValueError("--novelty-threshold needs --novelty")
+        novelty = _load_novelty(args) if args.novelty else None
         rc = RealtimeClassifier(model, out=sys.stdout, stats=args.stats, stats_out=sys.stderr,
                                 prometheus_port=args.prometheus,
                                 confidence=confidence, min_confidence=args.min_confidence,
                                 smooth=args.smooth, switch_margin=args.switch_margin,
-                                summary=args.summary)
-    except ValueError as e:  # --smooth or --switch-margin out of range, --summary over 8 classes
+                                summary=args.summary, novelty=novelty,
+                                novelty_threshold=args.novelty_threshold)
+    except ValueError as e:  # --smooth, --switch-margin or --novelty-threshold out of range,
+        # --summary over 8 classes, a detector's checkpoint in a classifier's place
         print(f"ERROR: {e}", file=sys.stderr)
         return 2
     try:

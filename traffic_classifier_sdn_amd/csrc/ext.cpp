@@ -224,6 +224,44 @@ static std::vector<Tensor> rf_predict_scores(Tensor X, Tensor nodes,
   return {proba, labels, conf};
 }
 
+// Isolation forest novelty score (iforest_kernels.hip) over the packed tables
+// of ops/cpu.py iforest_pack, whose node words are iforest_pack's to get
+// right.  Returns (score [n] f32, flags [n] u8, labels_out [n] i32 or an
+// empty tensor, psum [n] f64 or an empty tensor).  `labels` is an int32 [n]
+// tensor or None; `depth_cut` may be -inf (nothing is flagged).
+static std::vector<Tensor> iforest_score(Tensor X, Tensor nodes, Tensor roots,
+                                         OptTensor labels, double inv_denom,
+                                         double depth_cut, bool want_sum) {
+  const int64_t n = rows12(X, "X", kF32);
+  check_in(nodes, "nodes", kI32);
+  check_in(roots, "roots", kI32);
+  TORCH_CHECK(nodes.dim() == 2 && nodes.size(1) == 2 && nodes.size(0) >= 1,
+              "nodes must be (n_nodes,2) int32");
+  TORCH_CHECK(roots.dim() == 1, "roots must be (n_trees)");
+  const int64_t T = roots.size(0);
+  check_range(T, 1, 4096, "iforest_score", "trees");
+  TORCH_CHECK(std::isfinite(inv_denom) && inv_denom > 0.0,
+              "inv_denom must be finite and positive");
+  TORCH_CHECK(!std::isnan(depth_cut), "depth_cut must not be NaN");
+  if (labels.has_value())
+    TORCH_CHECK(labels->dim() == 1, "labels must be (n)");
+  const int* lab = opt_ptr<int>(labels, "labels", kI32, n, X);
+  const CUDAGuard guard = same_device("iforest_score", X, nodes, roots);
+  auto score = torch::empty({n}, X.options());
+  auto flags = torch::empty({n}, X.options().dtype(kU8));
+  auto labels_out = torch::empty({lab ? n : 0}, X.options().dtype(kI32));
+  auto psum = torch::empty({want_sum ? n : 0}, X.options().dtype(kF64));
+  const int rc = launch_iforest_score(
+      X.data_ptr<float>(), u32(nodes), roots.data_ptr<int>(), lab,
+      score.data_ptr<float>(), want_sum ? psum.data_ptr<double>() : nullptr,
+      lab ? labels_out.data_ptr<int>() : nullptr,
+      flags.data_ptr<unsigned char>(), inv_denom, depth_cut, n, (int)T,
+      cur_stream());
+  TORCH_CHECK(rc == 0, "iforest_score: no kernel for ", T, " trees");
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {score, flags, labels_out, psum};
+}
+
 // Class probabilities and the soft vote (ensemble_kernels.hip).
 static Tensor gnb_proba(Tensor X, Tensor theta, Tensor inv_var, Tensor cconst) {
   const int64_t n = rows12(X, "X", kF32);
@@ -824,6 +862,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rf_predict", &rf_predict, "packed-forest traversal + vote");
   m.def("rf_predict_scores", &rf_predict_scores,
         "packed-forest traversal, all trees: (proba | empty, labels, conf)");
+  // The detector is no classifier op: it lives in a submodule of its own.
+  // (tests/test_binding_checks.py pins the list of the top-level ops, each of
+  // which it runs through its generic refusals; this op's refusals are in
+  // tests/test_iforest_kernel.py.)
+  auto novelty = m.def_submodule("novelty", "novelty detection next to the classifiers");
+  novelty.def("iforest_score", &iforest_score,
+              "isolation forest novelty: (score, flags, labels_out | empty, psum | empty)",
+              py::arg("X"), py::arg("nodes"), py::arg("roots"), py::arg("labels"),
+              py::arg("inv_denom"), py::arg("depth_cut"), py::arg("want_sum"));
   m.def("gnb_proba", &gnb_proba, "GaussianNB class probabilities (f64 softmax)");
   m.def("linear_proba", &linear_proba, "logistic class probabilities (f64 softmax)");
   m.def("knn_vote_proba", &knn_vote_proba, "neighbour vote fractions from top-k indices");

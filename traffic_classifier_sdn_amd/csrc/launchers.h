@@ -105,6 +105,19 @@ int launch_rf_scores(const float* X,           // [n,12]
                      float* conf,              // [n]
                      long long n, int T, int C, hipStream_t stream);
 
+// --- iforest_kernels.hip ---------------------------------------------------
+// nonzero: T outside 1..4096, or only one of labels_in and labels_out given
+int launch_iforest_score(const float* X,         // [n,12]
+                         const unsigned* nodes,  // [n_nodes,2] packed uint2
+                         const int* roots,       // [T]
+                         const int* labels_in,   // [n] or null
+                         float* score,           // [n]
+                         double* psum,           // [n] or null
+                         int* labels_out,        // [n] or null, with labels_in
+                         unsigned char* flags,   // [n]
+                         double inv_denom, double depth_cut, long long n, int T,
+                         hipStream_t stream);
+
 // --- ensemble_kernels.hip --------------------------------------------------
 // each nonzero for a class or member count out of range
 int launch_gnb_proba(const float* X,         // [n,12]

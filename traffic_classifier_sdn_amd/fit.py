@@ -4,7 +4,7 @@ SURVEY.md §2.1 C9 / §3.4).
 
     python -m traffic_classifier_sdn_amd.fit [--algos all] [--out models]
         [--device cuda|cpu] [--sklearn-pickles] [--test-size 0.5] [--seed 101]
-        [--svc-probability]
+        [--svc-probability] [--isolation-forest]
 
 Per algorithm it reproduces the notebook protocol exactly: load the shipped
 per-class CSVs, dropna, drop the 4 cumulative columns (12 model features),
@@ -134,9 +134,34 @@ def fit_one(
     return result
 
 
+def fit_isolation_forest(Xtr, Xte, yte, device: Optional[str]) -> Dict:
+    """The novelty detector of `--novelty` (models/isolation_forest.py), fitted
+    on the train rows; reports the share of held-out rows it flags, overall
+    and per class: the price of the detector on known traffic."""
+    from .models import IsolationForest
+
+    t0 = time.perf_counter()
+    model = IsolationForest(device=device).fit(Xtr)
+    fit_s = time.perf_counter() - t0
+    novel = model.predict_novel(Xte)
+    yte = np.asarray(yte).astype(str)
+    return {
+        "algo": "isolation_forest",
+        "fit_seconds": fit_s,
+        "threshold": model.threshold_,
+        "n_nodes": int(sum(len(t["left"]) for t in model.trees_)),
+        "heldout_flagged": float(novel.mean()),
+        "heldout_flagged_per_class": {
+            c: float(novel[yte == c].mean()) for c in sorted(set(yte))
+        },
+        "_model": model,
+    }
+
+
 def main(argv: Optional[Sequence[str]] = None) -> int:
     ap = argparse.ArgumentParser(description=__doc__)
-    ap.add_argument("--algos", default="all", help="comma list of %s or 'all'" % ",".join(ALGOS))
+    ap.add_argument("--algos", default="all",
+                    help="comma list of %s, 'all', or 'none' (with --isolation-forest)" % ",".join(ALGOS))
     ap.add_argument("--out", default="models", help="checkpoint output directory")
     ap.add_argument("--device", default=None, help="cpu / cuda (default: auto)")
     ap.add_argument("--data-dir", default=None, help="training CSV directory (default: shipped dataset)")
@@ -156,6 +181,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                          "Platt sigmoids per class pair, written into its checkpoint, "
                          "so that 'svm --confidence' and an ensemble can use it "
                          "(not with a sharded fit)")
+    ap.add_argument("--isolation-forest", action="store_true",
+                    help="also fit the novelty detector of 'serve --novelty' on the train "
+                         "rows, write IsolationForest.npz and report the share of held-out "
+                         "rows it flags per class")
     args = ap.parse_args(argv)
 
     # torchrun-aware: initialize the group if launched with a WORLD_SIZE
@@ -181,7 +210,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         X, y = load_reference_dataset(data_dir=args.data_dir)
     Xtr, Xte, ytr, yte = train_test_split_ref(X, y, test_size=args.test_size, random_state=args.seed)
 
-    algos = list(ALGOS) if args.algos == "all" else [a.strip().lower() for a in args.algos.split(",")]
+    if args.algos == "none":
+        algos = []
+    else:
+        algos = list(ALGOS) if args.algos == "all" else [a.strip().lower() for a in args.algos.split(",")]
     for a in algos:
         if a not in ALGOS:
             print(f"ERROR: unknown algo {a!r}; choices: {', '.join(ALGOS)}", file=sys.stderr)
@@ -230,6 +262,19 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 print(f"{'':13s} confusion (rows=true):\n{'':16s}{hdr}")
                 for cname, row in zip(CLASS_NAMES, cm):
                     print(f"{'':14s}{cname[:6]:>7s} " + " ".join(f"{v:7d}" for v in row))
+    if args.isolation_forest and rank == 0:  # a host fit of milliseconds: one rank
+        res = fit_isolation_forest(Xtr, Xte, yte, args.device)
+        npz_path = os.path.join(args.out, "IsolationForest.npz")
+        res.pop("_model").save(npz_path)
+        res["checkpoint"] = npz_path
+        if args.json:
+            print(json.dumps(res))
+        else:
+            print(f"{'isolation_forest':13s} threshold={res['threshold']:.4f}  "
+                  f"held-out flagged={100 * res['heldout_flagged']:.2f}%  "
+                  f"fit={res['fit_seconds']:.2f}s  -> {npz_path}")
+            print(f"{'':13s} flagged per class: " + "  ".join(
+                f"{c} {100 * v:.2f}%" for c, v in res["heldout_flagged_per_class"].items()))
     if dist.is_initialized():
         import torch
 

@@ -5,6 +5,7 @@ from typing import Any, Dict, Optional
 from .base import Estimator
 from .ensemble import SoftVoteEnsemble
 from .gaussian_nb import GaussianNB
+from .isolation_forest import IsolationForest
 from .kmeans import KMeans
 from .kneighbors import KNeighborsClassifier
 from .logistic import LogisticRegression
@@ -19,6 +20,8 @@ _KIND_TO_CLASS = {
     "kneighbors": KNeighborsClassifier,
     "svc": SVC,
     "random_forest": RandomForestClassifier,
+    # a novelty detector, not a classifier: no entry in ALGO_TO_CHECKPOINT
+    "isolation_forest": IsolationForest,
 }
 
 # reference CLI subcommand -> (checkpoint file name, kind)
@@ -59,6 +62,7 @@ __all__ = [
     "Estimator",
     "FlowSmoother",
     "GaussianNB",
+    "IsolationForest",
     "KMeans",
     "KNeighborsClassifier",
     "LogisticRegression",

@@ -30,6 +30,11 @@ class SoftVoteEnsemble(Estimator):
         if not 1 <= len(members) <= 8:
             raise ValueError(f"a soft-vote ensemble takes 1..8 members, got {len(members)}")
         for name, m in members.items():
+            if getattr(m, "kind", "") == "isolation_forest":
+                raise ValueError(
+                    f"ensemble member {name!r} is an IsolationForest, a novelty detector "
+                    "with no class probabilities: it cannot vote"
+                )
             if not hasattr(m, "predict_proba_device") or getattr(m, "classes_", None) is None:
                 raise ValueError(
                     f"ensemble member {name!r} ({type(m).__name__}) has no class probabilities"

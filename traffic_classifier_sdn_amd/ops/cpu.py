@@ -512,6 +512,275 @@ def rf_predict_scores(
 
 
 # ----------------------------------------------------------------------
+# Isolation forest novelty score (CPU oracle of csrc/iforest_kernels.hip)
+# ----------------------------------------------------------------------
+
+_EULER_GAMMA = 0.5772156649015329
+
+# what the packed node and the exact f64 sum hold (see iforest_pack)
+IFOREST_MAX_TREES = 4096
+IFOREST_MAX_H = 64.0
+IFOREST_MAX_NODES = (1 << 24) - 1
+
+
+def iforest_c(n) -> np.ndarray:
+    """Average path length of an unsuccessful search in a binary search tree
+    of n rows, f64: 0 for n <= 1, 1 for n == 2, else
+    2 (ln(n - 1) + gamma) - 2 (n - 1) / n."""
+    n = np.asarray(n, dtype=np.float64)
+    big = np.maximum(n, 3.0)
+    c = 2.0 * (np.log(big - 1.0) + _EULER_GAMMA) - 2.0 * (big - 1.0) / big
+    return np.where(n <= 1.0, 0.0, np.where(n <= 2.0, 1.0, c))
+
+
+def _f32_round_down(v: np.ndarray) -> np.ndarray:
+    """The largest f32 <= each f64 value: the only f32 threshold t with
+    (x <= t) == (x <= v) for EVERY f32 x.  A plain cast rounds to nearest and
+    may land above v, which sends the f32 just above v to the wrong child."""
+    v = np.asarray(v, dtype=np.float64)
+    with np.errstate(over="ignore"):
+        t = v.astype(np.float32)
+    above = t.astype(np.float64) > v
+    t[above] = np.nextafter(t[above], np.float32(-np.inf))
+    return t
+
+
+def iforest_flatten(trees, max_samples: int) -> Dict[str, torch.Tensor]:
+    """Isolation trees -> the SoA layout of rf_flatten, with a leaf value in
+    place of a class distribution.
+
+    Each tree is a dict of per-node arrays ``left``, ``right``, ``feature``,
+    ``threshold`` (f64) and ``n_node_samples``, a leaf having ``left == -1``,
+    in depth-first order with ``left == index + 1`` (checked here).
+    ``max_samples`` is psi, the rows each tree was grown on.
+
+    ``threshold`` is the largest f32 <= the f64 threshold (_f32_round_down).
+    ``leaf_h`` holds, per leaf, h = depth + c(n_node_samples), computed in f64
+    and rounded once to f32; 0 for an inner node.
+    """
+    all_thr, all_right, all_feat, all_h = [], [], [], []
+    offsets = [0]
+    for t in trees:
+        left = np.asarray(t["left"], dtype=np.int64)
+        right = np.asarray(t["right"], dtype=np.int64)
+        feat = np.asarray(t["feature"], dtype=np.int64)
+        thr = np.asarray(t["threshold"], dtype=np.float64)
+        nns = np.asarray(t["n_node_samples"], dtype=np.float64)
+        n = left.shape[0]
+        is_leaf = left == -1
+        inner = np.nonzero(~is_leaf)[0]
+        if n < 1 or not (
+            np.all(left[inner] == inner + 1)
+            and np.all(right[inner] > inner + 1)
+            and np.all(right[inner] < n)
+        ):
+            raise ValueError("isolation tree is not in depth-first order (left == index + 1)")
+        depth = np.zeros(n, dtype=np.int64)
+        for i in inner:  # children follow their parent
+            depth[left[i]] = depth[i] + 1
+            depth[right[i]] = depth[i] + 1
+        h = depth.astype(np.float64) + iforest_c(nns)
+        all_thr.append(np.where(is_leaf, np.float32(0.0), _f32_round_down(thr)))
+        all_right.append(np.where(is_leaf, 0, right).astype(np.int32))
+        all_feat.append(np.where(is_leaf, -1, feat).astype(np.int32))
+        all_h.append(np.where(is_leaf, h, 0.0).astype(np.float32))
+        offsets.append(offsets[-1] + n)
+    if not all_thr:
+        raise ValueError("an isolation forest needs at least one tree")
+    return {
+        "threshold": torch.from_numpy(np.concatenate(all_thr).astype(np.float32)),
+        "right": torch.from_numpy(np.concatenate(all_right)),
+        "feature": torch.from_numpy(np.concatenate(all_feat)),
+        "leaf_h": torch.from_numpy(np.concatenate(all_h)),
+        "tree_offset": torch.tensor(offsets, dtype=torch.int32),
+        "max_samples": torch.tensor(int(max_samples), dtype=torch.int32),
+    }
+
+
+def _iforest_layout(forest: Dict[str, torch.Tensor]):
+    """(offsets i64 [T+1], right_global i64 [n_nodes], next_root i64
+    [n_nodes]) of a flattened forest, on the host."""
+    offsets = forest["tree_offset"].cpu().to(torch.int64)
+    counts = offsets[1:] - offsets[:-1]
+    n_nodes = forest["feature"].numel()
+    if (
+        offsets.numel() < 2 or int(offsets[0]) != 0 or int(offsets[-1]) != n_nodes
+        or bool((counts < 1).any())
+    ):
+        raise ValueError("tree_offset must rise from 0 to n_nodes, one or more nodes per tree")
+    base = torch.repeat_interleave(offsets[:-1], counts)
+    next_root = torch.repeat_interleave(offsets[1:], counts)
+    return offsets, forest["right"].cpu().to(torch.int64) + base, next_root
+
+
+def iforest_consts(forest: Dict[str, torch.Tensor]) -> Tuple[int, float, float]:
+    """(T, c(psi), inv_denom = 1 / (T c(psi))), the last two as f64; cached in
+    the forest dict, so that a forest on a device is read back once and not
+    in every (possibly captured) pass."""
+    consts = forest.get("_consts")
+    if consts is None:
+        T = forest["tree_offset"].numel() - 1
+        psi = int(forest["max_samples"])
+        if psi < 2:
+            raise ValueError(f"an isolation forest needs max_samples >= 2, got {psi}")
+        c_psi = float(iforest_c(psi))
+        consts = forest["_consts"] = (T, c_psi, 1.0 / (T * c_psi))
+    return consts
+
+
+def iforest_depth_cut(threshold, T: int, c_psi: float) -> float:
+    """The f64 path-length sum below which a row is novel:
+    score > threshold  <=>  psum < -log2(threshold) T c(psi).  ``None`` gives
+    -inf: nothing is flagged.  ValueError unless 0 < threshold < 1."""
+    if threshold is None:
+        return float("-inf")
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.floating)):
+        raise ValueError(f"threshold must be None or a float in (0, 1), got {threshold!r}")
+    thr = float(threshold)
+    if not 0.0 < thr < 1.0:
+        raise ValueError(f"threshold must be inside (0, 1), got {threshold!r}")
+    return -float(np.log2(thr)) * T * c_psi
+
+
+def iforest_pack(forest: Dict[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
+    """Pack a flattened isolation forest into the kernels' uint2 node table.
+
+    ``nodes``, n_nodes entries in rf_pack's layout:
+      inner: word0 = f32 threshold bits, word1 = (right_child_GLOBAL << 8) | feature
+      leaf:  word0 = f32 bits of h = depth + c(n_node_samples), word1 = 0xff
+    ``roots`` are the T root indices.
+
+    ValueError for what the kernels or the exact sum cannot hold: a right
+    child that does not lie after its parent's left child inside the same
+    tree (a tree not in depth-first order), a feature outside 0..11, more
+    than 4096 trees, a leaf value that is not 0 or in [1, 64) (with 4096
+    trees the f64 sum of such values stays an exact multiple of 2^-23 below
+    2^18), more than 2^24 - 1 nodes (the child link has 24 bits).
+    """
+    n_nodes = forest["feature"].numel()
+    n_trees = forest["tree_offset"].numel() - 1
+    if n_trees > IFOREST_MAX_TREES:
+        raise ValueError(f"the isolation forest kernels take at most 4096 trees, got {n_trees}")
+    if n_nodes > IFOREST_MAX_NODES:
+        raise ValueError(f"packed node format holds at most 2^24 - 1 nodes, got {n_nodes}")
+    offsets, right_global, next_root = _iforest_layout(forest)
+    feat = forest["feature"].cpu().to(torch.int64)
+    thr = forest["threshold"].cpu().to(torch.float32)
+    leaf_h = forest["leaf_h"].cpu().to(torch.float32)
+    index = torch.arange(n_nodes, dtype=torch.int64)
+    is_leaf = feat < 0
+    if bool((feat[~is_leaf] > 11).any()):
+        raise ValueError("an isolation tree splits on a feature outside 0..11")
+    ok = (right_global > index + 1) & (right_global < next_root)
+    if not bool(ok[~is_leaf].all()):
+        raise ValueError(
+            "isolation tree is not in depth-first order: a right child must lie after "
+            "its parent's left child, inside the same tree"
+        )
+    # (every link so stays inside its tree and points forward: a walk ends)
+    h = leaf_h[is_leaf]
+    if not bool(((h == 0) | ((h >= 1) & (h < IFOREST_MAX_H))).all()):
+        raise ValueError("a leaf value h = depth + c(n) must be 0 or in [1, 64)")
+    consts = iforest_consts(forest)
+    w0 = torch.where(is_leaf, leaf_h, thr).view(torch.int32)
+    w1 = torch.where(is_leaf, torch.tensor(0xFF, dtype=torch.int64), (right_global << 8) | feat)
+    # bits 31 of word1 are set from 2^23 nodes on: keep the bit pattern
+    w1 = torch.where(w1 >= 1 << 31, w1 - (1 << 32), w1).to(torch.int32)
+    nodes = torch.stack([w0, w1], dim=1).contiguous()
+    return {
+        "nodes": nodes.to(device),
+        "roots": offsets[:-1].to(torch.int32).to(device),
+        "n_trees": consts[0],
+        "c_psi": consts[1],
+        "inv_denom": consts[2],
+    }
+
+
+def iforest_score_check(X, forest, threshold, labels) -> float:
+    """Argument rules of iforest_score, shared by the CPU and GPU bindings:
+    no cast and no copy is made for the caller, so a wrong dtype or layout is
+    an error.  Returns depth_cut (iforest_depth_cut)."""
+    if not isinstance(X, torch.Tensor):
+        raise ValueError(f"iforest_score takes a tensor, got {type(X).__name__}")
+    if X.dim() != 2 or X.shape[1] != len(_FEATURE_NAMES):
+        raise ValueError(f"iforest_score takes (n, 12) features, got {tuple(X.shape)}")
+    if X.dtype != torch.float32:
+        raise ValueError(f"iforest_score takes f32 features, got {X.dtype}")
+    if not X.is_contiguous():
+        raise ValueError("X must be contiguous")
+    n = X.shape[0]
+    if labels is not None:
+        if (
+            not isinstance(labels, torch.Tensor)
+            or labels.dtype != torch.int32
+            or tuple(labels.shape) != (n,)
+            or not labels.is_contiguous()
+            or labels.device != X.device
+        ):
+            raise ValueError(f"labels must be None or a contiguous int32 ({n},) tensor on X's device")
+    T, c_psi, _ = iforest_consts(forest)
+    if not 1 <= T <= IFOREST_MAX_TREES:
+        raise ValueError(f"iforest_score takes 1..4096 trees, got {T}")
+    return iforest_depth_cut(threshold, T, c_psi)
+
+
+def iforest_leaves(X: torch.Tensor, forest: Dict[str, torch.Tensor]) -> torch.Tensor:
+    """int64 [n, T]: the GLOBAL index of the leaf each row reaches in each
+    tree.  Level-synchronous: all rows advance one level in all trees per
+    iteration.  ``x <= thr`` is false for a NaN, which so goes right."""
+    dev = X.device
+    offsets, right_global, _ = _iforest_layout(forest)
+    feat = forest["feature"].to(dev).long()
+    thr = forest["threshold"].to(dev)
+    right_global = right_global.to(dev)
+    n = X.shape[0]
+    idx = offsets[:-1].to(dev).unsqueeze(0).expand(n, -1).contiguous()
+    while True:
+        f = feat[idx]
+        leaf = f < 0
+        if bool(leaf.all()):
+            return idx
+        xv = X.gather(1, f.clamp(min=0))
+        nxt = torch.where(xv <= thr[idx], idx + 1, right_global[idx])
+        idx = torch.where(leaf, idx, nxt)
+
+
+def iforest_score(
+    X: torch.Tensor,
+    forest: Dict[str, torch.Tensor],
+    threshold: Optional[float] = None,
+    labels: Optional[torch.Tensor] = None,
+    want_sum: bool = False,
+) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """(score f32 [n], flags u8 [n], labels_out int32 [n] | None, psum f64 [n]
+    | None) of a flattened isolation forest (iforest_flatten).
+
+    psum is the sum over the trees of the leaf value h = depth + c(n_leaf) a
+    row reaches; every h is a multiple of 2^-23 below 64, so the f64 sum is
+    exact in any order.  score = 2^(-psum / (T c(psi))) in (0, 1], higher
+    meaning more anomalous (sklearn's -score_samples).  A row is flagged when
+    psum < depth_cut = -log2(threshold) T c(psi), which is score > threshold
+    decided on the exact sum; ``threshold=None`` flags nothing.  With
+    ``labels``, labels_out is -1 for a flagged row and its label otherwise,
+    so that class_traffic counts flagged rows as unknown.
+    """
+    depth_cut = iforest_score_check(X, forest, threshold, labels)
+    inv_denom = iforest_consts(forest)[2]
+    leaf_h = forest["leaf_h"].to(X.device)
+    n = X.shape[0]
+    psum = torch.empty(n, dtype=torch.float64, device=X.device)
+    for lo in range(0, n, 32768):  # bounds the [rows, T] index matrices
+        leaves = iforest_leaves(X[lo : lo + 32768], forest)
+        psum[lo : lo + 32768] = leaf_h[leaves].double().sum(dim=1)
+    score = torch.exp2(-psum * inv_denom).to(torch.float32)
+    novel = psum < depth_cut
+    labels_out = None
+    if labels is not None:
+        labels_out = torch.where(novel, torch.full_like(labels, -1), labels)
+    return score, novel.to(torch.uint8), labels_out, (psum if want_sum else None)
+
+
+# ----------------------------------------------------------------------
 # Class probabilities as f32 tensors, and the soft vote over them (CPU
 # oracles of csrc/ensemble_kernels.hip)
 # ----------------------------------------------------------------------

@@ -401,6 +401,48 @@ def rf_predict_proba(X: torch.Tensor, forest: Dict[str, torch.Tensor]) -> torch.
 
 
 # ----------------------------------------------------------------------
+# isolation forest novelty score (csrc/iforest_kernels.hip)
+# ----------------------------------------------------------------------
+
+iforest_c = _cpu.iforest_c
+iforest_flatten = _cpu.iforest_flatten
+iforest_pack = _cpu.iforest_pack
+iforest_consts = _cpu.iforest_consts
+iforest_depth_cut = _cpu.iforest_depth_cut
+iforest_score_check = _cpu.iforest_score_check
+iforest_leaves = _cpu.iforest_leaves  # cold: the parity tests' per-tree leaves
+
+
+def _iforest_packed(X: torch.Tensor, forest: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The isolation forest's packed tables on X's device, cached in the
+    forest dict."""
+    packed = forest.get("_packed")
+    if packed is None or packed["nodes"].device != X.device:
+        packed = iforest_pack(forest, X.device)
+        forest["_packed"] = packed
+    return packed
+
+
+def iforest_score(
+    X: torch.Tensor,
+    forest: Dict[str, torch.Tensor],
+    threshold: Optional[float] = None,
+    labels: Optional[torch.Tensor] = None,
+    want_sum: bool = False,
+) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    # no cast and no copy: the captured serve pass hands its own buffers over
+    depth_cut = _cpu.iforest_score_check(X, forest, threshold, labels)
+    if not X.is_cuda:
+        raise ValueError("the isolation forest kernels take GPU tensors, got a CPU tensor")
+    packed = _iforest_packed(X, forest)
+    score, flags, labels_out, psum = _ext.novelty.iforest_score(
+        X, packed["nodes"], packed["roots"], labels, packed["inv_denom"], depth_cut,
+        bool(want_sum),
+    )
+    return score, flags, (labels_out if labels is not None else None), (psum if want_sum else None)
+
+
+# ----------------------------------------------------------------------
 # class probabilities and the soft vote (csrc/ensemble_kernels.hip)
 # ----------------------------------------------------------------------
 

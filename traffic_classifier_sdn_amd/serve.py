@@ -113,8 +113,36 @@ class RealtimeClassifier:
         switch_margin: float = 0.0,
         summary: bool = False,
         prometheus_registry=None,
+        novelty: Optional[Estimator] = None,
+        novelty_threshold: Optional[float] = None,
     ) -> None:
+        if getattr(model, "kind", "") == "isolation_forest":
+            raise ValueError(
+                "an IsolationForest is a novelty detector with no classes to predict: "
+                "pass it as novelty=, next to a classifier"
+            )
         self.model = model
+        # novelty=IsolationForest: a flow whose novelty score is above the
+        # threshold (the detector's own by default) is shown as "unknown",
+        # after the confidence rule
+        self.novelty = None
+        self.last_novel: Optional[np.ndarray] = None  # bool[n] of the last pass
+        self.last_novelty_score: Optional[np.ndarray] = None  # float32[n]
+        if novelty is not None:
+            from .ops.cpu import iforest_depth_cut
+
+            if getattr(novelty, "kind", "") != "isolation_forest":
+                raise ValueError(
+                    f"novelty= takes an IsolationForest, got {type(novelty).__name__}"
+                )
+            if novelty.trees_ is None or novelty.threshold_ is None:
+                raise ValueError("novelty= takes a fitted IsolationForest")
+            thr = novelty.threshold_ if novelty_threshold is None else novelty_threshold
+            iforest_depth_cut(thr, 1, 1.0)  # ValueError unless inside (0, 1)
+            self.novelty = novelty
+            self.novelty_threshold = float(thr)
+        elif novelty_threshold is not None:
+            raise ValueError("novelty_threshold needs novelty=")
         # summary=True: flows, packets/s and bytes/s per class after each
         # pass (ops.class_traffic on the model's device), as a second table,
         # in the --stats line and in the Prometheus gauges
@@ -170,6 +198,22 @@ class RealtimeClassifier:
             )
 
     def classify_now(self) -> np.ndarray:
+        pred = self._classify_now()
+        if self.novelty is not None:
+            n = len(self.parser.table)
+            if n == 0:
+                self.last_novel = np.zeros(0, dtype=bool)
+                self.last_novelty_score = np.zeros(0, dtype=np.float32)
+            else:
+                X = self.parser.table.feature_matrix(dtype=np.float32)
+                score, flags, _ = self.novelty.novelty_device(X, None, self.novelty_threshold)
+                self.last_novelty_score = score.cpu().numpy()
+                self.last_novel = flags.cpu().numpy().astype(bool)
+                pred = np.asarray(pred, dtype=object)
+                pred[self.last_novel] = "unknown"
+        return pred
+
+    def _classify_now(self) -> np.ndarray:
         table = self.parser.table
         if len(table) == 0:
             if self.confidence:
@@ -274,6 +318,8 @@ class RealtimeClassifier:
                 if conf is not None:
                     line["mean_confidence"] = float(conf.mean()) if n else None
                     line["unknown"] = int((conf < self.min_confidence).sum())
+                if self.novelty is not None:
+                    line["novel"] = int(self.last_novel.sum())
                 if self.summary:
                     line["traffic"] = traffic_rates(self.traffic_classes, totals)
                 self.stats_out.write(json.dumps(line) + "\n")

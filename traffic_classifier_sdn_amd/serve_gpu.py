@@ -33,6 +33,14 @@ ops.class_traffic, flow count and the 12 feature sums per class and for
 a flow whose confidence is below it counts as unknown.  The reduction runs
 in the captured graph on the features that exist only on the device; one
 table of under 1 KB comes back instead of them.
+
+``novelty=model`` (an IsolationForest) scores every flow for how unlike the
+training rows it is (csrc/iforest_kernels.hip), in the same captured pass on
+the same features: after ``classify``, ``engine.novelty_score`` holds the
+f32 [n] scores and ``engine.novel`` the bool [n] flags (score above
+``novelty_threshold``, by default the model's own).  The result dict does not
+change.  With ``traffic=`` the flagged flows count as unknown: the score
+kernel hands the accounting that key's labels with -1 in the flagged rows.
 """
 
 from __future__ import annotations
@@ -54,6 +62,11 @@ class GpuServeEngine:
     traffic: Optional[np.ndarray] = None
     traffic_classes: Optional[List[str]] = None
     _traffic_key: Optional[str] = None
+    # likewise set per instance only with novelty=: after classify(), the
+    # f32 [n] novelty scores and the bool [n] flags of the pass
+    novelty_score: Optional[np.ndarray] = None
+    novel: Optional[np.ndarray] = None
+    _novelty = None
 
     def __init__(
         self,
@@ -68,7 +81,15 @@ class GpuServeEngine:
         switch_margin: float = 0.0,
         traffic: Optional[str] = None,
         traffic_min_confidence: float = 0.0,
+        novelty: Optional[Estimator] = None,
+        novelty_threshold: Optional[float] = None,
     ) -> None:
+        for name, m in models.items():
+            if getattr(m, "kind", "") == "isolation_forest":
+                raise ValueError(
+                    f"model {name!r} is an IsolationForest, a novelty detector with no classes "
+                    "to predict: pass it as novelty=, not among the models"
+                )
         self.models = models
         self.capacity = capacity
         self.device = torch.device(device)
@@ -175,6 +196,23 @@ class GpuServeEngine:
             self.h_nlive = torch.zeros(1, dtype=torch.int32, pin_memory=pin)
             self._h_nlive_np = self.h_nlive.numpy()  # same memory, cheap to set
             self.d_nlive = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if novelty is not None:
+            from . import ops
+
+            if getattr(novelty, "kind", "") != "isolation_forest":
+                raise ValueError(
+                    f"novelty= takes an IsolationForest, got {type(novelty).__name__}"
+                )
+            if novelty.trees_ is None or novelty.threshold_ is None:
+                raise ValueError("novelty= takes a fitted IsolationForest")
+            thr = novelty.threshold_ if novelty_threshold is None else novelty_threshold
+            ops.iforest_depth_cut(thr, 1, 1.0)  # ValueError unless inside (0, 1)
+            self._novelty = novelty.to(str(self.device))
+            self._novelty_threshold = float(thr)
+            self.d_nov: Dict[str, torch.Tensor] = {}
+            self.h_nov: Dict[str, torch.Tensor] = {}
+        elif novelty_threshold is not None:
+            raise ValueError("novelty_threshold needs novelty=")
         self.confidence: Dict[str, np.ndarray] = {}
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self.last_latency_s = 0.0
@@ -186,11 +224,15 @@ class GpuServeEngine:
         X = ops.flow_features(self.d_cur, self.d_prev, self.d_times)
         staged = self.smoother is not None or self._traffic_key is not None
         n_live = self.d_nlive if staged else None
+        if self._novelty is not None and self._traffic_key is None:
+            self._score_novelty(X, None)
         for name, labels, conf in self._predict_all(X, n_live):
             if conf is not None:
                 self._keep(self.d_conf, self.h_conf, name, conf)
             self._keep(self.d_labels, self.h_labels, name, labels)
             if name == self._traffic_key:
+                if self._novelty is not None:  # flagged flows count as unknown
+                    labels = self._score_novelty(X, labels)
                 # rows past the live count hold counters of earlier polls
                 totals = self._account(X, labels, conf, n_live)
                 if self._d_traffic is None:
@@ -200,6 +242,20 @@ class GpuServeEngine:
                     )
                 else:
                     self._d_traffic.copy_(totals)
+
+    def _novelty_pass(self, X: torch.Tensor, labels: Optional[torch.Tensor]):
+        """(score, flags, labels with -1 in the flagged rows | None): the one
+        run of the score kernel of a pass."""
+        if labels is not None and labels.dtype != torch.int32:  # a CPU model's int64 argmax
+            labels = labels.to(torch.int32)
+        return self._novelty.novelty_device(X, labels, self._novelty_threshold)
+
+    def _score_novelty(self, X: torch.Tensor, labels: Optional[torch.Tensor]):
+        """_novelty_pass into the static buffers; returns the masked labels."""
+        score, flags, masked = self._novelty_pass(X, labels)
+        self._keep(self.d_nov, self.h_nov, "score", score)
+        self._keep(self.d_nov, self.h_nov, "flags", flags)
+        return masked
 
     def _account(self, X: torch.Tensor, labels: torch.Tensor,
                  conf: Optional[torch.Tensor], n_live: Optional[torch.Tensor]) -> torch.Tensor:
@@ -321,6 +377,9 @@ class GpuServeEngine:
                 self.h_conf[name].copy_(self.d_conf[name], non_blocking=True)
             if self._traffic_key is not None:
                 self._h_traffic.copy_(self._d_traffic, non_blocking=True)
+            if self._novelty is not None:
+                for key in self.h_nov:
+                    self.h_nov[key].copy_(self.d_nov[key], non_blocking=True)
             torch.cuda.synchronize()
             for name in keys:
                 out[name] = self.h_labels[name][:n].numpy().copy()
@@ -329,6 +388,8 @@ class GpuServeEngine:
             }
             if self._traffic_key is not None:
                 self.traffic = self._h_traffic.numpy().copy()
+            if self._novelty is not None:
+                self._publish_novelty(self.h_nov["score"][:n], self.h_nov["flags"][:n])
         else:
             self.d_cur.copy_(self.h_cur)
             self.d_prev.copy_(self.h_prev)
@@ -340,8 +401,14 @@ class GpuServeEngine:
             }
             if self._traffic_key is not None:
                 self.traffic = self._d_traffic.numpy().copy()
+            if self._novelty is not None:
+                self._publish_novelty(self.d_nov["score"][:n], self.d_nov["flags"][:n])
         self.last_latency_s = time.perf_counter() - t0
         return out
+
+    def _publish_novelty(self, score: torch.Tensor, flags: torch.Tensor) -> None:
+        self.novelty_score = score.cpu().numpy().copy()
+        self.novel = flags.cpu().numpy().astype(bool)
 
     def _classify_unbounded(self, table: FlowTable) -> Dict[str, np.ndarray]:
         from . import ops
@@ -354,11 +421,16 @@ class GpuServeEngine:
         X = ops.flow_features(to(cur), to(prev), to(times))
         out = {}
         self.confidence = {}
+        if self._novelty is not None and self._traffic_key is None:
+            self._publish_novelty(*self._novelty_pass(X, None)[:2])
         for name, labels, conf in self._predict_all(X):
             if conf is not None:
                 self.confidence[name] = conf.cpu().numpy()
             out[name] = labels.cpu().numpy()
             if name == self._traffic_key:  # every row of X is a live flow
+                if self._novelty is not None:
+                    score, flags, labels = self._novelty_pass(X, labels)
+                    self._publish_novelty(score, flags)
                 self.traffic = self._account(X, labels, conf, None).cpu().numpy()
         self.last_latency_s = time.perf_counter() - t0
         return out

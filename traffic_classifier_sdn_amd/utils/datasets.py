@@ -231,6 +231,29 @@ def synthesize_quake_rows(
     return X.astype(np.float64), y
 
 
+def replay_feature_rows(specs, n_rows: int, seed: int = 0) -> np.ndarray:
+    """(n_rows, 12) f64 model features of the synthetic flows ``specs``
+    (flow.replay.SynthFlowSpec) through the real collection path, as
+    synthesize_quake_rows takes it: replay -> flow-table update ->
+    training_matrix(), one row per flow per poll after two priming polls."""
+    from ..flow.parser import replay
+    from ..flow.replay import TelemetryReplaySource
+
+    src = TelemetryReplaySource(specs=list(specs), seed=seed)
+    table = None
+    for _ in range(2):
+        table = replay(src.poll(), table)
+    rows: List[np.ndarray] = []
+    total = 0
+    while total < n_rows:
+        table = replay(src.poll(), table)
+        mat = table.training_matrix().copy()
+        rows.append(mat)
+        total += mat.shape[0]
+    keep = [CSV_HEADER_COLUMNS.index(name) for name in FEATURE_NAMES]
+    return np.concatenate(rows)[:n_rows][:, keep].astype(np.float64)
+
+
 def load_six_class_dataset(
     data_dir: Optional[str] = None,
     features_only: bool = True,
