@@ -33,6 +33,7 @@ setup(
                 os.path.join(CSRC, "iforest_kernels.hip"),
                 os.path.join(CSRC, "ensemble_kernels.hip"),
                 os.path.join(CSRC, "traffic_kernels.hip"),
+                os.path.join(CSRC, "top_flows_kernels.hip"),
                 os.path.join(CSRC, "svc_kernels.hip"),
                 os.path.join(CSRC, "knn_mfma.hip"),
                 os.path.join(CSRC, "fit_kernels.hip"),

@@ -173,6 +173,10 @@ def main(argv: Optional[list] = None) -> int:
                         help="below each flow table, print flows, packets/s and bytes/s per "
                              "traffic class (summed on the model's device); adds them to --stats "
                              "and --prometheus")
+    parser.add_argument("--top", type=int, default=None, metavar="K",
+                        help="needs --summary: below the summary, list the K flows of every "
+                             "traffic class with the most bytes/s (selected on the model's "
+                             "device); adds them to --stats")
     parser.add_argument("--novelty", action="store_true",
                         help="show flows unlike the training data as 'unknown': an isolation "
                              "forest scores every flow on the model's device "
@@ -244,9 +248,10 @@ def main(argv: Optional[list] = None) -> int:
                                 confidence=confidence, min_confidence=args.min_confidence,
                                 smooth=args.smooth, switch_margin=args.switch_margin,
                                 summary=args.summary, novelty=novelty,
-                                novelty_threshold=args.novelty_threshold)
+                                novelty_threshold=args.novelty_threshold, top=args.top)
     except ValueError as e:  # --smooth, --switch-margin or --novelty-threshold out of range,
-        # --summary over 8 classes, a detector's checkpoint in a classifier's place
+        # --summary over 8 classes, a detector's checkpoint in a classifier's place,
+        # --top without --summary or outside 1..64
         print(f"ERROR: {e}", file=sys.stderr)
         return 2
     try:

@@ -436,6 +436,42 @@ static Tensor class_traffic(Tensor X, Tensor labels, int64_t n_classes,
   return totals;
 }
 
+// Returns (rows int32 [C + 1, k], keys f32 [C + 1, k]): per group the k live
+// rows with the largest key, the f32 sum of the columns in `col_mask`
+// (top_flows_kernels.hip); -1 and 0.0 where a group has fewer.  `conf` and
+// `n_live` as in class_traffic.
+static std::vector<Tensor> class_top_flows(Tensor X, Tensor labels,
+                                           int64_t n_classes, int64_t k,
+                                           int64_t col_mask, OptTensor conf,
+                                           double min_conf, OptTensor n_live) {
+  const int64_t n = rows12(X, "X", kF32);
+  check_in(labels, "labels", kI32);
+  TORCH_CHECK(labels.dim() == 1 && labels.size(0) == n, "labels must be (n)");
+  TORCH_CHECK(n <= INT32_MAX, "class_top_flows indexes rows with 32 bits, got ", n);
+  TORCH_CHECK(n_classes >= 2 && n_classes <= 8,
+              "no kernel for class_top_flows with ", n_classes, " classes (2..8)");
+  TORCH_CHECK(k >= 1 && k <= 64,
+              "no kernel for class_top_flows with k = ", k, " (1..64)");
+  check_range(col_mask, 1, 0xfff, "class_top_flows", "as the column mask");
+  const float* cf = opt_ptr<float>(conf, "conf", kF32, n, X);
+  const int* live = opt_ptr<int>(n_live, "n_live", kI32, 1, X);
+  const float mc = (float)min_conf;
+  TORCH_CHECK(std::isfinite(mc), "min_conf must be finite");
+  const int C = (int)n_classes;
+  const int nb = class_top_flows_blocks(n);
+  const CUDAGuard guard = same_device("class_top_flows", X, labels);
+  auto partial = torch::empty({(int64_t)nb * (C + 1) * k}, X.options().dtype(kI64));
+  auto rows = torch::empty({C + 1, k}, X.options().dtype(kI32));
+  auto keys = torch::empty({C + 1, k}, X.options());
+  const int rc = launch_class_top_flows(
+      X.data_ptr<float>(), labels.data_ptr<int>(), cf, live, mc,
+      (unsigned)col_mask, u64(partial), rows.data_ptr<int>(),
+      keys.data_ptr<float>(), n, C, (int)k, nb, cur_stream());
+  TORCH_CHECK(rc == 0, "no kernel for class_top_flows with ", C, " classes and k = ", k);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {rows, keys};
+}
+
 // SVC labels (Out = int, [n]) and decision values (Out = double, [n,npair])
 // of svc_kernels.hip take the same arguments through the same kernel bodies,
 // which index SV, dual, svclass and intercept by nsv and C alone: one check
@@ -884,6 +920,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "per-class flow count and f64 feature sums: totals [C + 1, 13]",
         py::arg("X"), py::arg("labels"), py::arg("n_classes"), py::arg("conf"),
         py::arg("min_conf"), py::arg("n_live"));
+  // Selection is no classifier op either: a submodule of its own, its
+  // refusals in tests/test_top_flows_kernel.py.
+  auto selection = m.def_submodule("selection", "selection over the classified flows");
+  selection.def("class_top_flows", &class_top_flows,
+                "per class and unknown, the k flows with the largest key: (rows, keys)",
+                py::arg("X"), py::arg("labels"), py::arg("n_classes"), py::arg("k"),
+                py::arg("col_mask"), py::arg("conf"), py::arg("min_conf"),
+                py::arg("n_live"));
   m.def("svc_predict", &svc_predict, "RBF Gram + OVO vote");
   m.def("svc_decision", &svc_decision, "RBF Gram + OVO decision values (f64)");
   m.def("svc_couple", &svc_couple,

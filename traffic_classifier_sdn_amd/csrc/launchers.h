@@ -163,6 +163,22 @@ int launch_class_traffic(const float* X,       // [n,12]
                          double* totals,       // [C+1,13]
                          long long n, int C, int nb, hipStream_t stream);
 
+// --- top_flows_kernels.hip -------------------------------------------------
+// blocks of the partial kernel for n rows; sizes `partial`
+int class_top_flows_blocks(long long n);
+// nonzero: C outside 2..8, k outside 1..64, col_mask 0 or past bit 11, nb < 1
+int launch_class_top_flows(const float* X,               // [n,12]
+                           const int* labels,            // [n]
+                           const float* conf,            // [n] or null
+                           const int* n_live,            // [1] or null
+                           float min_conf,
+                           unsigned col_mask,            // bit c: column c is in the key
+                           unsigned long long* partial,  // [nb,C+1,k]
+                           int* rows,                    // [C+1,k]
+                           float* keys,                  // [C+1,k]
+                           long long n, int C, int k, int nb,
+                           hipStream_t stream);
+
 // --- svc_kernels.hip -------------------------------------------------------
 // each nonzero for C outside 2..6; npair = C(C-1)/2
 int launch_svc_predict(const float* X,                // [n,12]

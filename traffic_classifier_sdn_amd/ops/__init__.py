@@ -13,6 +13,7 @@ import torch
 
 from . import cpu as _cpu
 from .cpu import TRAFFIC_COLUMNS  # noqa: F401  (a constant, not an op to dispatch)
+from .cpu import TOP_FLOW_COLUMNS  # noqa: F401  (likewise)
 
 _gpu = None
 _gpu_err: Exception | None = None

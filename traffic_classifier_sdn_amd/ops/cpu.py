@@ -1091,6 +1091,114 @@ def class_traffic(
 
 
 # ----------------------------------------------------------------------
+# Top talkers: the k largest flows of every class
+# ----------------------------------------------------------------------
+
+# the default key of class_top_flows: forward plus reverse instantaneous bytes
+# per second, what the summary's "Bytes share" is made of
+TOP_FLOW_COLUMNS = (
+    _FEATURE_NAMES.index("Forward Instantaneous Bytes per Second"),
+    _FEATURE_NAMES.index("Reverse Instantaneous Bytes per Second"),
+)
+TOP_FLOWS_MAX_K = 64
+
+
+def top_flow_columns_check(columns):
+    """The columns of a key: a non-empty tuple of distinct ints in 0..11, in
+    any order (they are added in ascending order).  Returns them sorted."""
+    if isinstance(columns, (str, bytes)) or not isinstance(columns, (tuple, list)):
+        raise ValueError(f"columns must be a tuple of ints, got {columns!r}")
+    cols = []
+    for c in columns:
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)):
+            raise ValueError(f"columns must be ints, got {c!r}")
+        if not 0 <= int(c) < len(_FEATURE_NAMES):
+            raise ValueError(f"columns must be in 0..11, got {c}")
+        cols.append(int(c))
+    if not cols:
+        raise ValueError("columns must name at least one column")
+    if len(set(cols)) != len(cols):
+        raise ValueError(f"columns names a column twice: {tuple(columns)}")
+    return tuple(sorted(cols))
+
+
+def top_flows_k_check(k):
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError(f"k must be an int, got {k!r}")
+    if not 1 <= int(k) <= TOP_FLOWS_MAX_K:
+        raise ValueError(f"class_top_flows lists 1..{TOP_FLOWS_MAX_K} flows per class, got {k}")
+    return int(k)
+
+
+def class_top_flows_check(X, labels, n_classes, k, columns, conf, min_conf, n_live):
+    """Argument rules of class_top_flows, shared by the CPU and GPU bindings:
+    class_traffic's for everything the two ops share.  Returns
+    (C, k, columns sorted, column bit mask, f32(min_conf) as a float)."""
+    try:
+        C, mc = class_traffic_check(X, labels, n_classes, conf, min_conf, n_live)
+    except ValueError as e:
+        raise ValueError(str(e).replace("class_traffic", "class_top_flows")) from None
+    k = top_flows_k_check(k)
+    cols = top_flow_columns_check(columns)
+    if X.shape[0] >= 2**31:
+        raise ValueError(f"class_top_flows indexes rows with 32 bits, got {X.shape[0]} rows")
+    return C, k, cols, sum(1 << c for c in cols), mc
+
+
+def class_top_flows(
+    X: torch.Tensor,
+    labels: torch.Tensor,
+    n_classes: int,
+    k: int,
+    columns=TOP_FLOW_COLUMNS,
+    conf: Optional[torch.Tensor] = None,
+    min_conf: float = 0.0,
+    n_live: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per class and for "unknown", the k live rows with the largest key:
+    (rows int32 [C + 1, k], keys f32 [C + 1, k]).
+
+    The group of a row is class_traffic's.  Its key is the f32 sum of
+    X[r, c] over ``columns``, added one at a time in ascending column order.
+    Within a group the larger key comes first and equal keys go by the lower
+    row; +0 and -0 are equal; a NaN key ranks above every number and NaNs tie
+    with each other.  Where a group has fewer than k rows the remaining cells
+    hold -1 and 0.0.
+    """
+    C, k, cols, _, mc = class_top_flows_check(
+        X, labels, n_classes, k, columns, conf, min_conf, n_live
+    )
+    n = X.shape[0]
+    dev = X.device
+    rows = torch.full((C + 1, k), -1, dtype=torch.int32, device=dev)
+    keys = torch.zeros(C + 1, k, dtype=torch.float32, device=dev)
+    if n_live is not None:
+        n = min(n, max(int(n_live[0]), 0))
+    if n == 0:
+        return rows, keys
+    key = X[:n, cols[0]].clone()
+    for c in cols[1:]:
+        key = key + X[:n, c]
+    lab = labels[:n].long()
+    known = (lab >= 0) & (lab < C)
+    if conf is not None:
+        known &= ~(conf[:n] < mc)
+    group = torch.where(known, lab, torch.full_like(lab, C))
+    nan = torch.isnan(key)
+    # what the order compares: -0 becomes +0, a NaN stands above +inf through
+    # the second sort; both sorts are stable, so ties keep the lower row first
+    value = torch.where(nan, torch.full_like(key, float("inf")), key + 0.0)
+    for g in range(C + 1):
+        idx = torch.nonzero(group == g).squeeze(1)
+        idx = idx[torch.argsort(value[idx], descending=True, stable=True)]
+        idx = idx[torch.argsort(nan[idx].to(torch.int8), descending=True, stable=True)]
+        idx = idx[:k]
+        rows[g, : idx.numel()] = idx.to(torch.int32)
+        keys[g, : idx.numel()] = key[idx]
+    return rows, keys
+
+
+# ----------------------------------------------------------------------
 # Serve-path feature extraction (CPU oracle of the GPU kernel; mirrors the
 # reference Flow update math, traffic_classifier.py:63-96)
 # ----------------------------------------------------------------------

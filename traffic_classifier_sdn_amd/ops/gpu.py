@@ -530,6 +530,30 @@ def class_traffic(
     return _ext.class_traffic(X, labels, C, conf, mc, n_live)
 
 
+class_top_flows_check = _cpu.class_top_flows_check
+top_flow_columns_check = _cpu.top_flow_columns_check
+top_flows_k_check = _cpu.top_flows_k_check
+TOP_FLOW_COLUMNS = _cpu.TOP_FLOW_COLUMNS
+
+
+def class_top_flows(
+    X: torch.Tensor,
+    labels: torch.Tensor,
+    n_classes: int,
+    k: int,
+    columns=TOP_FLOW_COLUMNS,
+    conf: Optional[torch.Tensor] = None,
+    min_conf: float = 0.0,
+    n_live: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    # no cast and no copy, as in class_traffic
+    C, k, _, mask, mc = _cpu.class_top_flows_check(
+        X, labels, n_classes, k, columns, conf, min_conf, n_live
+    )
+    rows, keys = _ext.selection.class_top_flows(X, labels, C, k, mask, conf, mc, n_live)
+    return rows, keys
+
+
 # ----------------------------------------------------------------------
 # fit ops
 # ----------------------------------------------------------------------

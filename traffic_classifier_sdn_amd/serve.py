@@ -84,6 +84,32 @@ def render_traffic_summary(classes, totals) -> str:
     return str(t)
 
 
+def top_flow_lists(classes, rows, rates) -> dict:
+    """{class: [[flow_id, Bps], ...]} out of ops.class_top_flows' results,
+    largest first, the padding left out."""
+    return {
+        name: [[int(r), float(v)] for r, v in zip(rows[g], rates[g]) if r >= 0]
+        for g, name in enumerate(classes)
+    }
+
+
+def render_top_flows(table: FlowTable, classes, rows, rates, totals) -> str:
+    """The table below the summary: one line per listed flow, largest first
+    within its class; a class with no flows has no line.  The share is the
+    flow's rate over its class's forward plus reverse bytes per second."""
+    class_bytes = {
+        name: r["fwd_Bps"] + r["rev_Bps"] for name, r in traffic_rates(classes, totals).items()
+    }
+    t = Table(["Traffic Type", "Flow ID", "Src MAC", "Dest MAC", "B/s", "Share of class"])
+    metas = table.metas()
+    for name, flows in top_flow_lists(classes, rows, rates).items():
+        for flow_id, rate in flows:
+            share = rate / class_bytes[name] if class_bytes[name] != 0 else 0.0
+            t.add_row([name, flow_id, metas[flow_id].ethsrc, metas[flow_id].ethdst,
+                       "%.1f" % rate, "%.1f%%" % (100.0 * share)])
+    return str(t)
+
+
 def map_cluster_labels(idx: np.ndarray) -> np.ndarray:
     """Integer cluster ids -> class names (reference label map,
     traffic_classifier.py:109-114)."""
@@ -115,6 +141,7 @@ class RealtimeClassifier:
         prometheus_registry=None,
         novelty: Optional[Estimator] = None,
         novelty_threshold: Optional[float] = None,
+        top: Optional[int] = None,
     ) -> None:
         if getattr(model, "kind", "") == "isolation_forest":
             raise ValueError(
@@ -164,6 +191,19 @@ class RealtimeClassifier:
             self.traffic_classes = names + ["unknown"]
             self._class_index = {n: i for i, n in enumerate(names)}
             self._last_X = np.zeros((0, 12), dtype=np.float32)
+        # top=K (with summary): the K flows of every class with the most
+        # bytes per second (ops.class_top_flows on the same features and
+        # labels), as a third table and in the --stats line.  No Prometheus
+        # series: a label per flow has no bound.
+        self.top = None
+        self.top_flows: Optional[np.ndarray] = None  # int32 [C + 1, K] flow ids, -1: none
+        self.top_flow_rates: Optional[np.ndarray] = None  # f32 [C + 1, K]
+        if top is not None:
+            from .ops.cpu import top_flows_k_check
+
+            if not self.summary:
+                raise ValueError("top= lists the flows behind the summary: it needs summary=True")
+            self.top = top_flows_k_check(top)
         # smooth=alpha: labels and confidence come from the flow's class
         # probabilities averaged across passes (models/smoothing.py)
         self.smoother = None
@@ -274,8 +314,13 @@ class RealtimeClassifier:
             dtype=np.int32, count=len(labels),
         )
         X = torch.from_numpy(np.ascontiguousarray(self._last_X)).to(device)
-        totals = ops.class_traffic(X, torch.from_numpy(idx).to(device), C)
+        idx = torch.from_numpy(idx).to(device)
+        totals = ops.class_traffic(X, idx, C)
         self.traffic = totals.cpu().numpy()
+        if self.top is not None:
+            rows, rates = ops.class_top_flows(X, idx, C, self.top)
+            self.top_flows = rows.cpu().numpy()
+            self.top_flow_rates = rates.cpu().numpy()
         return self.traffic
 
     def feed(self, line) -> bool:
@@ -299,6 +344,10 @@ class RealtimeClassifier:
             if self.summary:
                 totals = self.account(labels)
                 self.out.write(render_traffic_summary(self.traffic_classes, totals) + "\n")
+                if self.top is not None:
+                    self.out.write(render_top_flows(
+                        self.parser.table, self.traffic_classes, self.top_flows,
+                        self.top_flow_rates, totals) + "\n")
             self.out.flush()
             if self.prom is not None:
                 self.prom.observe_pass(
@@ -322,6 +371,9 @@ class RealtimeClassifier:
                     line["novel"] = int(self.last_novel.sum())
                 if self.summary:
                     line["traffic"] = traffic_rates(self.traffic_classes, totals)
+                if self.top is not None:
+                    line["top_flows"] = top_flow_lists(
+                        self.traffic_classes, self.top_flows, self.top_flow_rates)
                 self.stats_out.write(json.dumps(line) + "\n")
                 self.stats_out.flush()
             return True

@@ -41,6 +41,15 @@ f32 [n] scores and ``engine.novel`` the bool [n] flags (score above
 ``novelty_threshold``, by default the model's own).  The result dict does not
 change.  With ``traffic=`` the flagged flows count as unknown: the score
 kernel hands the accounting that key's labels with -1 in the flagged rows.
+
+``top_flows=K`` (with ``traffic=``) lists, per class and for "unknown", the K
+flows with the largest rate (csrc/top_flows_kernels.hip): after ``classify``,
+``engine.top_flows`` holds the int32 [C + 1, K] flow-table slots (rows:
+``traffic_classes``; -1 where a class has fewer) and ``engine.top_flow_rates``
+the f32 [C + 1, K] rates, the sum of the feature columns
+``top_flows_columns`` (default ops.TOP_FLOW_COLUMNS, forward plus reverse
+bytes per second).  It ranks what the accounting counts, the same labels,
+confidence rule and live rows, right after it in the same captured pass.
 """
 
 from __future__ import annotations
@@ -67,6 +76,11 @@ class GpuServeEngine:
     novelty_score: Optional[np.ndarray] = None
     novel: Optional[np.ndarray] = None
     _novelty = None
+    # likewise set per instance only with top_flows=: after classify(), the
+    # int32 [C + 1, K] slots and the f32 [C + 1, K] rates of the pass
+    top_flows: Optional[np.ndarray] = None
+    top_flow_rates: Optional[np.ndarray] = None
+    _top_k: Optional[int] = None
 
     def __init__(
         self,
@@ -83,6 +97,8 @@ class GpuServeEngine:
         traffic_min_confidence: float = 0.0,
         novelty: Optional[Estimator] = None,
         novelty_threshold: Optional[float] = None,
+        top_flows: Optional[int] = None,
+        top_flows_columns: Optional[Sequence[int]] = None,
     ) -> None:
         for name, m in models.items():
             if getattr(m, "kind", "") == "isolation_forest":
@@ -190,6 +206,20 @@ class GpuServeEngine:
             self.traffic_classes = [str(c) for c in classes] + ["unknown"]
             self._d_traffic: Optional[torch.Tensor] = None
             self._h_traffic: Optional[torch.Tensor] = None
+        # the K largest flows of every class of that accounting
+        if top_flows is not None:
+            from .ops.cpu import TOP_FLOW_COLUMNS, top_flow_columns_check, top_flows_k_check
+
+            if traffic is None:
+                raise ValueError("top_flows= ranks the flows that traffic= accounts: it needs traffic=")
+            self._top_k = top_flows_k_check(top_flows)
+            self._top_columns = top_flow_columns_check(
+                TOP_FLOW_COLUMNS if top_flows_columns is None else tuple(top_flows_columns)
+            )
+            self.d_top: Dict[str, torch.Tensor] = {}
+            self.h_top: Dict[str, torch.Tensor] = {}
+        elif top_flows_columns is not None:
+            raise ValueError("top_flows_columns needs top_flows=")
         if self.smoother is not None or traffic is not None:
             # the live-row count, staged like the counters: the captured
             # pass runs over all `capacity` rows and reads it on the device
@@ -242,6 +272,10 @@ class GpuServeEngine:
                     )
                 else:
                     self._d_traffic.copy_(totals)
+                if self._top_k is not None:
+                    rows, rates = self._rank(X, labels, conf, n_live)
+                    self._keep(self.d_top, self.h_top, "rows", rows)
+                    self._keep(self.d_top, self.h_top, "rates", rates)
 
     def _novelty_pass(self, X: torch.Tensor, labels: Optional[torch.Tensor]):
         """(score, flags, labels with -1 in the flagged rows | None): the one
@@ -266,6 +300,19 @@ class GpuServeEngine:
         mc = self._traffic_min_conf
         return ops.class_traffic(
             X, labels, len(self.traffic_classes) - 1, conf if mc > 0.0 else None, mc, n_live
+        )
+
+    def _rank(self, X: torch.Tensor, labels: torch.Tensor,
+              conf: Optional[torch.Tensor], n_live: Optional[torch.Tensor]):
+        """(rows, rates) of ops.class_top_flows over what _account counts."""
+        from . import ops
+
+        if labels.dtype != torch.int32:  # a CPU model's int64 argmax
+            labels = labels.to(torch.int32)
+        mc = self._traffic_min_conf
+        return ops.class_top_flows(
+            X, labels, len(self.traffic_classes) - 1, self._top_k, self._top_columns,
+            conf if mc > 0.0 else None, mc, n_live,
         )
 
     def _keep(self, dev: Dict[str, torch.Tensor], host: Dict[str, torch.Tensor],
@@ -377,6 +424,9 @@ class GpuServeEngine:
                 self.h_conf[name].copy_(self.d_conf[name], non_blocking=True)
             if self._traffic_key is not None:
                 self._h_traffic.copy_(self._d_traffic, non_blocking=True)
+            if self._top_k is not None:
+                for key in self.h_top:
+                    self.h_top[key].copy_(self.d_top[key], non_blocking=True)
             if self._novelty is not None:
                 for key in self.h_nov:
                     self.h_nov[key].copy_(self.d_nov[key], non_blocking=True)
@@ -388,6 +438,9 @@ class GpuServeEngine:
             }
             if self._traffic_key is not None:
                 self.traffic = self._h_traffic.numpy().copy()
+            if self._top_k is not None:
+                self.top_flows = self.h_top["rows"].numpy().copy()
+                self.top_flow_rates = self.h_top["rates"].numpy().copy()
             if self._novelty is not None:
                 self._publish_novelty(self.h_nov["score"][:n], self.h_nov["flags"][:n])
         else:
@@ -401,6 +454,9 @@ class GpuServeEngine:
             }
             if self._traffic_key is not None:
                 self.traffic = self._d_traffic.numpy().copy()
+            if self._top_k is not None:
+                self.top_flows = self.d_top["rows"].numpy().copy()
+                self.top_flow_rates = self.d_top["rates"].numpy().copy()
             if self._novelty is not None:
                 self._publish_novelty(self.d_nov["score"][:n], self.d_nov["flags"][:n])
         self.last_latency_s = time.perf_counter() - t0
@@ -432,5 +488,9 @@ class GpuServeEngine:
                     score, flags, labels = self._novelty_pass(X, labels)
                     self._publish_novelty(score, flags)
                 self.traffic = self._account(X, labels, conf, None).cpu().numpy()
+                if self._top_k is not None:
+                    rows, rates = self._rank(X, labels, conf, None)
+                    self.top_flows = rows.cpu().numpy()
+                    self.top_flow_rates = rates.cpu().numpy()
         self.last_latency_s = time.perf_counter() - t0
         return out
