@@ -31,6 +31,7 @@ setup(
                 os.path.join(CSRC, "predict_kernels.hip"),
                 os.path.join(CSRC, "rf_proba_kernels.hip"),
                 os.path.join(CSRC, "iforest_kernels.hip"),
+                os.path.join(CSRC, "rf_explain_kernels.hip"),
                 os.path.join(CSRC, "ensemble_kernels.hip"),
                 os.path.join(CSRC, "traffic_kernels.hip"),
                 os.path.join(CSRC, "top_flows_kernels.hip"),

@@ -16,6 +16,8 @@ across passes, for every model that has them (models/smoothing.py).
 each flow table (ops.class_traffic).
 `--novelty [--novelty-threshold S]` shows flows unlike the training data as
 'unknown', whatever the classifier says of them (models/isolation_forest.py).
+`Randomforest --explain` adds a "Why" column: the feature that adds most to
+the forest's probability of the class shown, and how much (ops.rf_explain).
 
 Telemetry sources:
   --source subprocess   spawn a monitor command (default: the in-package
@@ -184,6 +186,10 @@ def main(argv: Optional[list] = None) -> int:
     parser.add_argument("--novelty-threshold", type=float, default=None, metavar="S",
                         help="with --novelty: a flow is novel when its score in (0, 1) is "
                              "above S (default: the detector's own threshold)")
+    parser.add_argument("--explain", action="store_true",
+                        help="Randomforest only: add a 'Why' column, the feature that adds most "
+                             "to the forest's probability of the class shown and how much "
+                             "(computed on the model's device); adds feature counts to --stats")
     parser.add_argument("--members", default=DEFAULT_MEMBERS, metavar="A,B,...",
                         help="ensemble: the subcommand names of the member models")
     parser.add_argument("--weights", default=None, metavar="W,W,...",
@@ -238,6 +244,10 @@ def main(argv: Optional[list] = None) -> int:
         print(f"ERROR: {args.subcommand} has no class probabilities: no --smooth",
               file=sys.stderr)
         return 2
+    if args.explain and getattr(model, "kind", "") != "random_forest":
+        print(f"ERROR: {args.subcommand} is not a random forest: --explain explains a forest's "
+              "verdicts only", file=sys.stderr)
+        return 2
     # the streams as they are now, not as they were when serve was imported
     try:
         if args.novelty_threshold is not None and not args.novelty:
@@ -248,7 +258,8 @@ def main(argv: Optional[list] = None) -> int:
                                 confidence=confidence, min_confidence=args.min_confidence,
                                 smooth=args.smooth, switch_margin=args.switch_margin,
                                 summary=args.summary, novelty=novelty,
-                                novelty_threshold=args.novelty_threshold, top=args.top)
+                                novelty_threshold=args.novelty_threshold, top=args.top,
+                                explain=args.explain)
     except ValueError as e:  # --smooth, --switch-margin or --novelty-threshold out of range,
         # --summary over 8 classes, a detector's checkpoint in a classifier's place,
         # --top without --summary or outside 1..64

@@ -262,6 +262,48 @@ static std::vector<Tensor> iforest_score(Tensor X, Tensor nodes, Tensor roots,
   return {score, flags, labels_out, psum};
 }
 
+// Per-feature contributions to the probability of each row's class
+// (rf_explain_kernels.hip) over the classifier forest's packed `nodes` and
+// `roots` and the `delta` table of ops/cpu.py rf_explain_flatten, one row of
+// C steps per node.  Returns (contrib [n,12] f32 or an empty tensor, why [n]
+// i32, why_value [n] f32, sums [n,12] i64 or an empty tensor).  The range
+// refusals are the launcher's: its nonzero return is the error.
+static std::vector<Tensor> rf_explain(Tensor X, Tensor nodes, Tensor roots,
+                                      Tensor delta, Tensor labels,
+                                      bool want_matrix, bool want_sums) {
+  const int64_t n = rows12(X, "X", kF32);
+  check_in(nodes, "nodes", kI32);
+  check_in(roots, "roots", kI32);
+  check_in(delta, "delta", kI32);
+  check_in(labels, "labels", kI32);
+  TORCH_CHECK(nodes.dim() == 2 && nodes.size(1) == 2 && nodes.size(0) >= 1,
+              "nodes must be (n_nodes,2) int32");
+  TORCH_CHECK(roots.dim() == 1, "roots must be (n_trees)");
+  TORCH_CHECK(delta.dim() == 2 && delta.size(0) == nodes.size(0),
+              "delta must be (n_nodes,C): one row per node of nodes");
+  TORCH_CHECK(labels.dim() == 1 && labels.size(0) == n, "labels must be (n)");
+  const int64_t T = roots.size(0);
+  const int64_t C = delta.size(1);
+  TORCH_CHECK(T <= INT32_MAX && C <= INT32_MAX, "rf_explain: counts past 32 bits");
+  const CUDAGuard guard =
+      same_device("rf_explain", X, nodes, roots, delta, labels);
+  auto contrib = torch::empty({want_matrix ? n : 0, 12}, X.options());
+  auto why = torch::empty({n}, X.options().dtype(kI32));
+  auto why_value = torch::empty({n}, X.options());
+  auto sums = torch::empty({want_sums ? n : 0, 12}, X.options().dtype(kI64));
+  const int rc = launch_rf_explain(
+      X.data_ptr<float>(), u32(nodes), roots.data_ptr<int>(),
+      delta.data_ptr<int>(), labels.data_ptr<int>(),
+      want_matrix ? contrib.data_ptr<float>() : nullptr, why.data_ptr<int>(),
+      why_value.data_ptr<float>(),
+      want_sums ? reinterpret_cast<long long*>(sums.data_ptr<int64_t>()) : nullptr,
+      n, (int)T, (int)C, cur_stream());
+  TORCH_CHECK(rc == 0, "rf_explain: no kernel for ", C, " classes and ", T,
+              " trees (2..8 classes, 1..4096 trees)");
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {contrib, why, why_value, sums};
+}
+
 // Class probabilities and the soft vote (ensemble_kernels.hip).
 static Tensor gnb_proba(Tensor X, Tensor theta, Tensor inv_var, Tensor cconst) {
   const int64_t n = rows12(X, "X", kF32);
@@ -928,6 +970,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                 py::arg("X"), py::arg("labels"), py::arg("n_classes"), py::arg("k"),
                 py::arg("col_mask"), py::arg("conf"), py::arg("min_conf"),
                 py::arg("n_live"));
+  // Nor is the explanation: a submodule of its own, its refusals in
+  // tests/test_rf_explain_kernel.py.
+  auto explain = m.def_submodule("explain", "why a model gave a flow its class");
+  explain.def("rf_explain", &rf_explain,
+              "forest feature contributions: (contrib | empty, why, why_value, sums | empty)",
+              py::arg("X"), py::arg("nodes"), py::arg("roots"), py::arg("delta"),
+              py::arg("labels"), py::arg("want_matrix"), py::arg("want_sums"));
   m.def("svc_predict", &svc_predict, "RBF Gram + OVO vote");
   m.def("svc_decision", &svc_decision, "RBF Gram + OVO decision values (f64)");
   m.def("svc_couple", &svc_couple,

@@ -118,6 +118,19 @@ int launch_iforest_score(const float* X,         // [n,12]
                          double inv_denom, double depth_cut, long long n, int T,
                          hipStream_t stream);
 
+// --- rf_explain_kernels.hip ------------------------------------------------
+// nonzero: C outside 2..8 or T outside 1..4096
+int launch_rf_explain(const float* X,         // [n,12]
+                      const unsigned* nodes,  // [n_nodes,2] packed uint2
+                      const int* roots,       // [T]
+                      const int* delta,       // [n_nodes,C]
+                      const int* labels,      // [n]
+                      float* contrib,         // [n,12] or null, 16-B aligned
+                      int* why,               // [n]
+                      float* why_value,       // [n]
+                      long long* sums,        // [n,12] or null
+                      long long n, int T, int C, hipStream_t stream);
+
 // --- ensemble_kernels.hip --------------------------------------------------
 // each nonzero for a class or member count out of range
 int launch_gnb_proba(const float* X,         // [n,12]

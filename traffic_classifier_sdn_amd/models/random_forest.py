@@ -156,6 +156,7 @@ class RandomForestClassifier(Estimator):
         self.builder = builder
         self.trees_: Optional[List[Dict[str, np.ndarray]]] = None
         self._forest = None  # packed SoA (lazy)
+        self._explain_tables = None  # ops.cpu.rf_explain_flatten (lazy)
 
     def fit(self, X: ArrayLike, y: ArrayLike):
         Xn = np.asarray(as_tensor(X, torch.device("cpu"), torch.float64).numpy())
@@ -203,6 +204,7 @@ class RandomForestClassifier(Estimator):
         all_trees.sort(key=lambda p: p[0])
         self.trees_ = [t for _, t in all_trees]
         self._forest = None
+        self._explain_tables = None
         return self
 
     @property
@@ -216,9 +218,41 @@ class RandomForestClassifier(Estimator):
             }
         return self._forest
 
+    @property
+    def explain_tables(self):
+        """The per-node class-probability steps, the per-class bias and the
+        depth that ``explain`` works from (ops.cpu.rf_explain_flatten),
+        cached like ``forest``."""
+        if getattr(self, "_explain_tables", None) is None:
+            self._explain_tables = ops.cpu.rf_explain_flatten(self.trees_, len(self.classes_))
+        return self._explain_tables
+
     def predict_index(self, X: ArrayLike) -> torch.Tensor:
         Xt = as_tensor(X, self.device, torch.float32)
         return ops.rf_argmax(Xt, self.forest)
+
+    def explain_device(self, X: ArrayLike, labels=None, want_matrix: bool = True,
+                       want_sums: bool = False):
+        """(contrib f32[n,12] | None, why int32[n], why_value f32[n], sums
+        int64[n,12] | None) device tensors of ops.rf_explain: what each
+        feature adds to the probability of the class ``labels`` names (int32
+        class indices; None: the forest's own predict_index)."""
+        Xt = as_tensor(X, self.device, torch.float32).contiguous()
+        if labels is None:
+            labels = self.predict_index(Xt)
+        labels = torch.as_tensor(labels).to(device=Xt.device, dtype=torch.int32).contiguous()
+        return ops.rf_explain(Xt, self.forest, self.explain_tables, labels, want_matrix, want_sums)
+
+    def explain(self, X: ArrayLike):
+        """numpy (class names [n], contrib f32 [n,12], bias f64 [n]) of the
+        forest's own verdicts: bias + contrib.sum(1) is the probability
+        predict_proba gives the named class."""
+        Xt = as_tensor(X, self.device, torch.float32).contiguous()
+        idx = self.predict_index(Xt).to(torch.int32)
+        contrib = self.explain_device(Xt, idx)[0].cpu().numpy()
+        idx = idx.cpu().numpy()
+        names = idx if self.classes_ is None else self.classes_[idx]
+        return names, contrib, self.explain_tables["bias"].numpy()[idx]
 
     def predict_proba(self, X: ArrayLike) -> torch.Tensor:
         Xt = as_tensor(X, self.device, torch.float32)

@@ -512,6 +512,186 @@ def rf_predict_scores(
 
 
 # ----------------------------------------------------------------------
+# Forest feature contributions (CPU oracle of csrc/rf_explain_kernels.hip)
+# ----------------------------------------------------------------------
+
+# a step of a class probability is stored as rint(step * 2^30) in an int32
+RF_EXPLAIN_SCALE = float(1 << 30)
+# T * max_depth below this keeps |S| under 2^22 * 2^30 = 2^52, exact in f64
+RF_EXPLAIN_MAX_TERMS = 1 << 22
+RF_EXPLAIN_MAX_TREES = 4096
+
+
+def rf_explain_flatten(trees, n_classes: int) -> Dict[str, object]:
+    """The tables of rf_explain next to rf_flatten's, in its node order:
+    ``{"delta": int32 [n_nodes, C], "bias": f64 [C], "max_depth": int}``.
+
+    With p_v = values[v] / sum(values[v]) in f64 (rf_flatten's leaf
+    normalisation, here for every node), row w of ``delta`` holds
+    rint((p_w - p_parent(w)) * 2^30), half to even, and zeros for a root;
+    ``bias`` is the mean over the trees of p_root and ``max_depth`` the
+    longest path in edges.  ValueError when T * max_depth >= 2^22 (the sums of
+    rf_explain would leave the exact range), and for a tree that is not in
+    depth-first order.
+    """
+    C = int(n_classes)
+    deltas, roots = [], []
+    max_depth = 0
+    for t in trees:
+        left = np.asarray(t["left"], dtype=np.int64)
+        right = np.asarray(t["right"], dtype=np.int64)
+        values = np.asarray(t["values"], dtype=np.float64).reshape(left.shape[0], -1)
+        n = left.shape[0]
+        if values.shape[1] != C:
+            raise ValueError(f"a tree holds {values.shape[1]} classes per node, not {C}")
+        inner = np.nonzero(left != -1)[0]
+        if n < 1 or not (
+            np.all(left[inner] == inner + 1)
+            and np.all(right[inner] > inner + 1)
+            and np.all(right[inner] < n)
+        ):
+            raise ValueError("tree violates left_child == index+1 invariant")
+        p = values / np.clip(values.sum(axis=1, keepdims=True), 1e-30, None)
+        parent = np.zeros(n, dtype=np.int64)  # a root is its own parent: zeros
+        parent[left[inner]] = parent[right[inner]] = inner
+        # depth = number of ancestors, by pointer doubling: log2(depth) rounds
+        depth = (np.arange(n) > 0).astype(np.int64)
+        jump = parent
+        while jump.any():
+            depth = depth + depth[jump]
+            jump = jump[jump]
+        deltas.append(np.rint((p - p[parent]) * RF_EXPLAIN_SCALE).astype(np.int32))
+        roots.append(p[0])
+        max_depth = max(max_depth, int(depth.max()))
+    if not deltas:
+        raise ValueError("a forest needs at least one tree")
+    if len(deltas) * max_depth >= RF_EXPLAIN_MAX_TERMS:
+        raise ValueError(
+            f"{len(deltas)} trees of depth {max_depth} have 2^22 or more path edges: "
+            "the contribution sums would not stay exact"
+        )
+    return {
+        "delta": torch.from_numpy(np.ascontiguousarray(np.concatenate(deltas))),
+        "bias": torch.from_numpy(np.stack(roots).sum(axis=0) / len(roots)),
+        "max_depth": max_depth,
+    }
+
+
+def rf_explain_check(X, forest, tables, labels) -> Tuple[int, int]:
+    """Argument rules of rf_explain, shared by the CPU and GPU bindings: no
+    cast and no copy is made for the caller, so a wrong dtype or layout is an
+    error.  Returns (T, C)."""
+    for name, t in (("X", X), ("labels", labels)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"rf_explain takes tensors, got {type(t).__name__} for {name}")
+    if X.dim() != 2 or X.dtype != torch.float32 or not X.is_contiguous():
+        raise ValueError(
+            f"rf_explain takes contiguous f32 (n, features) rows, got {X.dtype} {tuple(X.shape)}"
+        )
+    n = X.shape[0]
+    if (
+        labels.dtype != torch.int32
+        or tuple(labels.shape) != (n,)
+        or not labels.is_contiguous()
+        or labels.device != X.device
+    ):
+        raise ValueError(f"labels must be a contiguous int32 ({n},) tensor on X's device")
+    T = forest["tree_offset"].numel() - 1
+    n_nodes = forest["feature"].numel()
+    delta = tables["delta"]
+    if (
+        not isinstance(delta, torch.Tensor)
+        or delta.dtype != torch.int32
+        or delta.dim() != 2
+        or delta.shape[0] != n_nodes
+        or delta.shape[1] < 1
+    ):
+        raise ValueError(f"tables['delta'] must be int32 ({n_nodes}, C): one row per node")
+    C = delta.shape[1]  # (the forest's own count may live on a device)
+    if T < 1 or T * int(tables["max_depth"]) >= RF_EXPLAIN_MAX_TERMS:
+        raise ValueError(
+            f"rf_explain takes a forest of 1 or more trees with T * max_depth < 2^22, got "
+            f"T = {T}, max_depth = {tables['max_depth']}"
+        )
+    top = forest.get("_max_feature")
+    if top is None:  # read back once, not in every (possibly captured) pass
+        top = forest["_max_feature"] = int(forest["feature"].max())
+    if top >= X.shape[1]:
+        raise ValueError(f"the forest splits on feature {top}, X has {X.shape[1]} columns")
+    return T, C
+
+
+def rf_explain(
+    X: torch.Tensor,
+    forest: Dict[str, torch.Tensor],
+    tables: Dict[str, object],
+    labels: torch.Tensor,
+    want_matrix: bool = True,
+    want_sums: bool = False,
+) -> Tuple[Optional[torch.Tensor], torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """Why the forest gives each row the class ``labels`` names: (contrib f32
+    [n, F] | None, why int32 [n], why_value f32 [n], sums int64 [n, F] |
+    None), the Saabas decomposition over rf_explain_flatten's ``tables``.
+
+    A row walks every tree by rf_predict_proba's rule (``x[f] <= threshold``
+    goes left, to the next entry; a NaN goes right).  sums[f] adds
+    delta[w, label] over all trees and all edges v -> w of the paths with
+    feature(v) = f: integers, so the sum is exact in any order.  contrib[f] =
+    (float)((double)sums[f] / (2^30 T)), and tables["bias"][label] +
+    sum(contrib) is the forest's probability of that class up to max_depth *
+    2^-31.  why is the first-maximum argmax of sums if that maximum is > 0,
+    else -1, and why_value = contrib[why], or 0.  A label outside [0, C) gives
+    zeros, -1 and 0.
+    """
+    T, C = rf_explain_check(X, forest, tables, labels)
+    dev = X.device
+    n, F = X.shape
+    offsets, right_global, _ = _iforest_layout(forest)
+    feat = forest["feature"].to(dev).long()
+    thr = forest["threshold"].to(dev)
+    right_global = right_global.to(dev)
+    delta = tables["delta"].to(dev).reshape(-1).long()
+    lab = labels.long()
+    known = (lab >= 0) & (lab < C)
+    col = torch.where(known, lab, torch.zeros_like(lab)).unsqueeze(1)
+    sums = torch.zeros(n, F, dtype=torch.int64, device=dev)
+    for lo in range(0, n, 32768):  # bounds the [rows, T] index matrices
+        x = X[lo : lo + 32768]
+        idx = offsets[:-1].to(dev).unsqueeze(0).expand(x.shape[0], -1).contiguous()
+        part = sums[lo : lo + 32768]
+        while True:
+            f = feat[idx]
+            leaf = f < 0
+            if bool(leaf.all()):
+                break
+            f = f.clamp(min=0)
+            nxt = torch.where(x.gather(1, f) <= thr[idx], idx + 1, right_global[idx])
+            nxt = torch.where(leaf, idx, nxt)
+            step = delta[nxt * C + col[lo : lo + 32768]]
+            part.scatter_add_(1, f, torch.where(leaf, torch.zeros_like(step), step))
+            idx = nxt
+    sums = torch.where(known.unsqueeze(1), sums, torch.zeros_like(sums))
+    contrib = (sums.double() / (RF_EXPLAIN_SCALE * T)).to(torch.float32)
+    if F:
+        best = sums.max(dim=1).values
+        # the first column that reaches the maximum (see ensemble_vote)
+        first = torch.argmax((sums == best.unsqueeze(1)).to(torch.uint8), dim=1)
+        why = torch.where(best > 0, first, torch.full_like(first, -1))
+        why_value = torch.where(
+            best > 0, contrib.gather(1, first.unsqueeze(1)).squeeze(1), torch.zeros_like(contrib[:, 0])
+        )
+    else:
+        why = torch.full((n,), -1, dtype=torch.int64, device=dev)
+        why_value = torch.zeros(n, dtype=torch.float32, device=dev)
+    return (
+        (contrib if want_matrix else None),
+        why.to(torch.int32),
+        why_value,
+        (sums if want_sums else None),
+    )
+
+
+# ----------------------------------------------------------------------
 # Isolation forest novelty score (CPU oracle of csrc/iforest_kernels.hip)
 # ----------------------------------------------------------------------
 

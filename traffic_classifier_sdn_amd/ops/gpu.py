@@ -401,6 +401,44 @@ def rf_predict_proba(X: torch.Tensor, forest: Dict[str, torch.Tensor]) -> torch.
 
 
 # ----------------------------------------------------------------------
+# forest feature contributions (csrc/rf_explain_kernels.hip)
+# ----------------------------------------------------------------------
+
+rf_explain_flatten = _cpu.rf_explain_flatten
+rf_explain_check = _cpu.rf_explain_check
+
+
+def _rf_explain_delta(X: torch.Tensor, tables: Dict[str, object]) -> torch.Tensor:
+    """The delta table on X's device, cached in the tables dict."""
+    delta = tables.get("_delta")
+    if delta is None or delta.device != X.device:
+        delta = tables["_delta"] = tables["delta"].to(X.device).contiguous()
+    return delta
+
+
+def rf_explain(
+    X: torch.Tensor,
+    forest: Dict[str, torch.Tensor],
+    tables: Dict[str, object],
+    labels: torch.Tensor,
+    want_matrix: bool = True,
+    want_sums: bool = False,
+) -> Tuple[Optional[torch.Tensor], torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    # no cast and no copy: the captured serve pass hands its own buffers over
+    T, C = _cpu.rf_explain_check(X, forest, tables, labels)
+    if X.shape[1] != 12 or not 2 <= C <= 8:  # the kernels' schema and class range
+        return _cpu.rf_explain(X, forest, tables, labels, want_matrix, want_sums)
+    if T > _cpu.RF_EXPLAIN_MAX_TREES:
+        raise ValueError(f"the forest explain kernels take at most 4096 trees, got {T}")
+    packed = _rf_packed(X, forest)
+    contrib, why, why_value, sums = _ext.explain.rf_explain(
+        X, packed["nodes"], packed["roots"], _rf_explain_delta(X, tables), labels,
+        bool(want_matrix), bool(want_sums),
+    )
+    return (contrib if want_matrix else None), why, why_value, (sums if want_sums else None)
+
+
+# ----------------------------------------------------------------------
 # isolation forest novelty score (csrc/iforest_kernels.hip)
 # ----------------------------------------------------------------------
 

@@ -23,16 +23,29 @@ import numpy as np
 from .flow.parser import PollStreamParser
 from .flow.state import FlowTable
 from .models.base import Estimator
-from .utils.schema import CLASS_NAMES, CSV_HEADER
+from .utils.schema import CLASS_NAMES, CSV_HEADER, FEATURE_SHORT_NAMES
 from .utils.table import Table
 
 
-def render_flow_table(table: FlowTable, labels, confidence=None) -> str:
+def why_cells(why, why_value) -> list:
+    """One cell per flow for the "Why" column: the short name of the feature
+    that adds most to the probability of the class shown and what it adds,
+    "Rev avg B/s +0.21"; blank where no feature speaks for it (why < 0)."""
+    return [
+        "%s %+.2f" % (FEATURE_SHORT_NAMES[f], v) if f >= 0 else ""
+        for f, v in zip(why, why_value)
+    ]
+
+
+def render_flow_table(table: FlowTable, labels, confidence=None, why=None) -> str:
     """The reference's console table (traffic_classifier.py:100-118); with
-    ``confidence`` (one value per flow) a last column shows it."""
+    ``confidence`` (one value per flow) a further column shows it, and with
+    ``why`` (one cell per flow, see why_cells) a last column "Why"."""
     cols = ["Flow ID", "Src MAC", "Dest MAC", "Traffic Type", "Forward Status", "Reverse Status"]
     if confidence is not None:
         cols.append("Confidence")
+    if why is not None:
+        cols.append("Why")
     t = Table(cols)
     metas = table.metas()
     statuses = table.statuses()
@@ -40,6 +53,8 @@ def render_flow_table(table: FlowTable, labels, confidence=None) -> str:
         row = [i, meta.ethsrc, meta.ethdst, labels[i], fs, rs]
         if confidence is not None:
             row.append("%.2f" % confidence[i])
+        if why is not None:
+            row.append(why[i])
         t.add_row(row)
     return str(t)
 
@@ -142,6 +157,7 @@ class RealtimeClassifier:
         novelty: Optional[Estimator] = None,
         novelty_threshold: Optional[float] = None,
         top: Optional[int] = None,
+        explain: bool = False,
     ) -> None:
         if getattr(model, "kind", "") == "isolation_forest":
             raise ValueError(
@@ -149,6 +165,20 @@ class RealtimeClassifier:
                 "pass it as novelty=, next to a classifier"
             )
         self.model = model
+        # explain=True: per flow, the feature that adds most to the forest's
+        # probability of the class SHOWN (smoothed if smoothing is on; a flow
+        # shown as "unknown" gets none) and what it adds (ops.rf_explain on
+        # the model's device), as a "Why" column and in the --stats line
+        self.explain = bool(explain)
+        self.last_why: Optional[np.ndarray] = None  # int32[n] feature index, -1: none
+        self.last_why_value: Optional[np.ndarray] = None  # float32[n]
+        if self.explain:
+            if getattr(model, "kind", "") != "random_forest" or not hasattr(model, "explain_device"):
+                raise ValueError(
+                    f"{type(model).__name__} is not a random forest: only a forest's verdicts "
+                    "are explained"
+                )
+            self._explain_index = {str(c): i for i, c in enumerate(model.classes_)}
         # novelty=IsolationForest: a flow whose novelty score is above the
         # threshold (the detector's own by default) is shown as "unknown",
         # after the confidence rule
@@ -251,7 +281,25 @@ class RealtimeClassifier:
                 self.last_novel = flags.cpu().numpy().astype(bool)
                 pred = np.asarray(pred, dtype=object)
                 pred[self.last_novel] = "unknown"
+        if self.explain:
+            self._explain_now(pred)
         return pred
+
+    def _explain_now(self, pred) -> None:
+        """Why of the classes shown: a name that is no class of the forest
+        ("unknown") is label -1, which the op answers with no feature."""
+        n = len(self.parser.table)
+        if n == 0:
+            self.last_why = np.zeros(0, dtype=np.int32)
+            self.last_why_value = np.zeros(0, dtype=np.float32)
+            return
+        shown = np.fromiter(
+            (self._explain_index.get(str(name), -1) for name in pred), dtype=np.int32, count=n
+        )
+        X = self.parser.table.feature_matrix(dtype=np.float32)
+        _, why, why_value, _ = self.model.explain_device(X, shown, want_matrix=False)
+        self.last_why = why.cpu().numpy()
+        self.last_why_value = why_value.cpu().numpy()
 
     def _classify_now(self) -> np.ndarray:
         table = self.parser.table
@@ -340,7 +388,12 @@ class RealtimeClassifier:
             labels = self.classify_now()
             predict_s = time.perf_counter() - t0
             conf = self.last_confidence if self.confidence else None
-            self.out.write(render_flow_table(self.parser.table, labels, conf) + "\n")
+            if self.explain:
+                flow_table = render_flow_table(
+                    self.parser.table, labels, conf, why_cells(self.last_why, self.last_why_value))
+            else:
+                flow_table = render_flow_table(self.parser.table, labels, conf)
+            self.out.write(flow_table + "\n")
             if self.summary:
                 totals = self.account(labels)
                 self.out.write(render_traffic_summary(self.traffic_classes, totals) + "\n")
@@ -369,6 +422,11 @@ class RealtimeClassifier:
                     line["unknown"] = int((conf < self.min_confidence).sum())
                 if self.novelty is not None:
                     line["novel"] = int(self.last_novel.sum())
+                if self.explain:
+                    feats, counts = np.unique(self.last_why[self.last_why >= 0], return_counts=True)
+                    line["why"] = {
+                        FEATURE_SHORT_NAMES[f]: int(c) for f, c in zip(feats, counts)
+                    }
                 if self.summary:
                     line["traffic"] = traffic_rates(self.traffic_classes, totals)
                 if self.top is not None:

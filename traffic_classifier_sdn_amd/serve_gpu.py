@@ -50,6 +50,17 @@ the f32 [C + 1, K] rates, the sum of the feature columns
 ``top_flows_columns`` (default ops.TOP_FLOW_COLUMNS, forward plus reverse
 bytes per second).  It ranks what the accounting counts, the same labels,
 confidence rule and live rows, right after it in the same captured pass.
+
+``explain=name`` (a random forest among the models) says why that forest
+gave each flow its class (csrc/rf_explain_kernels.hip), in the same captured
+pass on the same features and on the forest's own labels of the pass, not
+masked by novelty: after ``classify``, ``engine.why`` holds the int32 [n]
+index into ``engine.explain_features`` of the feature that adds most to the
+class's probability (-1: none adds anything) and ``engine.why_value`` the
+f32 [n] amount it adds.  ``explain_matrix=True`` also leaves
+``engine.contributions``, f32 [n, 12]: with ``engine.explain_bias`` (f64 [C])
+of the flow's class they add up to the forest's probability of that class.
+The result dict does not change.
 """
 
 from __future__ import annotations
@@ -81,6 +92,15 @@ class GpuServeEngine:
     top_flows: Optional[np.ndarray] = None
     top_flow_rates: Optional[np.ndarray] = None
     _top_k: Optional[int] = None
+    # likewise set per instance only with explain=: after classify(), the
+    # int32 [n] feature index and the f32 [n] contribution of the pass, and
+    # with explain_matrix=True the f32 [n, 12] contributions
+    why: Optional[np.ndarray] = None
+    why_value: Optional[np.ndarray] = None
+    contributions: Optional[np.ndarray] = None
+    explain_bias: Optional[np.ndarray] = None
+    explain_features: Optional[tuple] = None
+    _explain: Optional[str] = None
 
     def __init__(
         self,
@@ -99,6 +119,8 @@ class GpuServeEngine:
         novelty_threshold: Optional[float] = None,
         top_flows: Optional[int] = None,
         top_flows_columns: Optional[Sequence[int]] = None,
+        explain: Optional[str] = None,
+        explain_matrix: bool = False,
     ) -> None:
         for name, m in models.items():
             if getattr(m, "kind", "") == "isolation_forest":
@@ -243,6 +265,31 @@ class GpuServeEngine:
             self.h_nov: Dict[str, torch.Tensor] = {}
         elif novelty_threshold is not None:
             raise ValueError("novelty_threshold needs novelty=")
+        if explain is not None:
+            from .utils.schema import FEATURE_SHORT_NAMES
+
+            if explain not in models:
+                raise ValueError(f"explain={explain!r} is not a key of models")
+            forest = models[explain]
+            if getattr(forest, "kind", "") != "random_forest" or not hasattr(forest, "explain_device"):
+                raise ValueError(
+                    f"explain={explain!r} holds a {type(forest).__name__}, not a random forest: "
+                    "only a forest's verdicts are explained"
+                )
+            if forest.trees_ is None:
+                raise ValueError("explain= takes a fitted forest")
+            if not 2 <= len(forest.classes_) <= 8:
+                raise ValueError(
+                    f"explain= explains forests of 2..8 classes, {explain!r} has {len(forest.classes_)}"
+                )
+            self._explain = explain
+            self._explain_matrix = bool(explain_matrix)
+            self.explain_bias = forest.explain_tables["bias"].numpy().copy()
+            self.explain_features = FEATURE_SHORT_NAMES
+            self.d_exp: Dict[str, torch.Tensor] = {}
+            self.h_exp: Dict[str, torch.Tensor] = {}
+        elif explain_matrix:
+            raise ValueError("explain_matrix needs explain=")
         self.confidence: Dict[str, np.ndarray] = {}
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self.last_latency_s = 0.0
@@ -260,6 +307,9 @@ class GpuServeEngine:
             if conf is not None:
                 self._keep(self.d_conf, self.h_conf, name, conf)
             self._keep(self.d_labels, self.h_labels, name, labels)
+            if name == self._explain:
+                for key, value in self._explain_pass(X, labels).items():
+                    self._keep(self.d_exp, self.h_exp, key, value)
             if name == self._traffic_key:
                 if self._novelty is not None:  # flagged flows count as unknown
                     labels = self._score_novelty(X, labels)
@@ -290,6 +340,25 @@ class GpuServeEngine:
         self._keep(self.d_nov, self.h_nov, "score", score)
         self._keep(self.d_nov, self.h_nov, "flags", flags)
         return masked
+
+    def _explain_pass(self, X: torch.Tensor, labels: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """{"why", "why_value"[, "contrib"]} of the explained forest's own
+        labels: the one run of the explain kernel of a pass."""
+        if labels.dtype != torch.int32:
+            labels = labels.to(torch.int32)
+        contrib, why, why_value, _ = self.models[self._explain].explain_device(
+            X, labels, want_matrix=self._explain_matrix
+        )
+        out = {"why": why, "why_value": why_value}
+        if self._explain_matrix:
+            out["contrib"] = contrib
+        return out
+
+    def _publish_explain(self, got: Dict[str, torch.Tensor], n: int) -> None:
+        self.why = got["why"][:n].cpu().numpy().copy()
+        self.why_value = got["why_value"][:n].cpu().numpy().copy()
+        if self._explain_matrix:
+            self.contributions = got["contrib"][:n].cpu().numpy().copy()
 
     def _account(self, X: torch.Tensor, labels: torch.Tensor,
                  conf: Optional[torch.Tensor], n_live: Optional[torch.Tensor]) -> torch.Tensor:
@@ -430,6 +499,9 @@ class GpuServeEngine:
             if self._novelty is not None:
                 for key in self.h_nov:
                     self.h_nov[key].copy_(self.d_nov[key], non_blocking=True)
+            if self._explain is not None:
+                for key in self.h_exp:
+                    self.h_exp[key].copy_(self.d_exp[key], non_blocking=True)
             torch.cuda.synchronize()
             for name in keys:
                 out[name] = self.h_labels[name][:n].numpy().copy()
@@ -443,6 +515,8 @@ class GpuServeEngine:
                 self.top_flow_rates = self.h_top["rates"].numpy().copy()
             if self._novelty is not None:
                 self._publish_novelty(self.h_nov["score"][:n], self.h_nov["flags"][:n])
+            if self._explain is not None:
+                self._publish_explain(self.h_exp, n)
         else:
             self.d_cur.copy_(self.h_cur)
             self.d_prev.copy_(self.h_prev)
@@ -459,6 +533,8 @@ class GpuServeEngine:
                 self.top_flow_rates = self.d_top["rates"].numpy().copy()
             if self._novelty is not None:
                 self._publish_novelty(self.d_nov["score"][:n], self.d_nov["flags"][:n])
+            if self._explain is not None:
+                self._publish_explain(self.d_exp, n)
         self.last_latency_s = time.perf_counter() - t0
         return out
 
@@ -483,6 +559,8 @@ class GpuServeEngine:
             if conf is not None:
                 self.confidence[name] = conf.cpu().numpy()
             out[name] = labels.cpu().numpy()
+            if name == self._explain:
+                self._publish_explain(self._explain_pass(X, labels), len(table))
             if name == self._traffic_key:  # every row of X is a live flow
                 if self._novelty is not None:
                     score, flags, labels = self._novelty_pass(X, labels)

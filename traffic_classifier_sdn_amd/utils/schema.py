@@ -38,6 +38,23 @@ FEATURE_NAMES = (
 )
 NUM_FEATURES = len(FEATURE_NAMES)
 
+# The same 12 features in the words of the serve tables' headings ("Fwd B/s"),
+# for a column that names one feature per flow.
+FEATURE_SHORT_NAMES = (
+    "Fwd dPkts",
+    "Fwd dBytes",
+    "Fwd pkt/s",
+    "Fwd avg pkt/s",
+    "Fwd B/s",
+    "Fwd avg B/s",
+    "Rev dPkts",
+    "Rev dBytes",
+    "Rev pkt/s",
+    "Rev avg pkt/s",
+    "Rev B/s",
+    "Rev avg B/s",
+)
+
 # Cumulative counter columns present in training CSVs but dropped before
 # fitting (reference: notebooks/1_log_Kmeans.ipynb cell 18).
 CUMULATIVE_NAMES = (
